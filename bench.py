@@ -6,6 +6,12 @@ BASELINE.json metric "Mpkt/s + GiB/s device-resident parse+cksum, 64B & IMIX,
 launch) over one batch of synthetic frames already resident in HBM. Default
 workload = BASELINE configs[1]: 16M x 64-B Eth/IPv4/UDP frames per GPU.
 
+A plain run sets up, warms up, times --steps steps and prints the line;
+--dump-outputs DIR also writes what the last step computed. Everything else
+(CPU baselines, stream ceilings, the other output kinds, the IMIX / malformed /
+real-traffic / 52M-frame / serialize objects, the clock and latency probes)
+runs only with --full.
+
 Multi-GPU (torchrun, one process per GPU): each rank regenerates its own
 16M-frame shard from the global index range [rank*F, (rank+1)*F) — weak
 scaling, no data-path collective; only a barrier and a MAX over ranks of the
@@ -310,6 +316,53 @@ def load_traffic(workload, out_kind):
         return None
 
 
+DUMP_BUDGET = 48 << 20  # bytes of arrays one --dump-outputs run writes at most
+DUMP_SEED = 0x6E6578  # of the frame sample taken from a batch over that budget
+
+
+def dump_sample(count, values):
+    """The frames --dump-outputs writes of a batch of `count` with `values`
+    float64 values per frame (and the frame's index): all of them, or as many
+    as DUMP_BUDGET holds, drawn without replacement from DUMP_SEED, ascending."""
+    n = min(count, DUMP_BUDGET // (8 * (values + 1)))
+    if n == count:
+        return np.arange(count)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(count, n, replace=False))
+
+
+def dump_outputs(path, eng, batch, out, out_kind, count, rank, world, stream, device):
+    """--dump-outputs: what the timed path's last step left in `out`, as its
+    caller reads it, one float64 array per field in `path`/<field>.npy. A
+    parse: the per-frame nexg_desc / nexg_record / flags / verdict fields;
+    grouped and sparse outputs are first expanded to nexg_desc on the device
+    (nexg_grouped_expand / nexg_sparse_expand), since the kernel leaves the
+    slots of those layouts that no frame uses unwritten. A build (`batch` is
+    None): the frames' bytes, `frame.npy` of shape (n, 42). A batch over
+    DUMP_BUDGET is sampled: the same sorted, seeded frame indices in every
+    run, written as frame_index.npy. The ranks of a multi-GPU run prefix
+    their files with rank<r>_."""
+    import torch
+    from nex_amd import abi
+    if batch is None:
+        rows, dt = out, np.dtype([("frame", "u1", (42,))])
+    elif out_kind in (abi.OUT_SPARSE, abi.OUT_GROUPED):
+        rows, dt = eng.sparse_expand(batch, out, grouped=out_kind == abi.OUT_GROUPED, stream=stream), abi.DESC_DTYPE
+    else:
+        rows, dt = out, {abi.OUT_DESC: abi.DESC_DTYPE, abi.OUT_RECORD: abi.RECORD_DTYPE,
+                         abi.OUT_FLAGS: abi.FLAGS_DTYPE, abi.OUT_VERDICT: abi.VERDICT_DTYPE}[out_kind]
+    idx = dump_sample(count, sum(int(np.prod(dt[n].shape)) for n in dt.names))
+    n = len(idx)
+    rows = rows[: count * dt.itemsize].view(count, dt.itemsize)[torch.from_numpy(idx).to(device)]
+    torch.cuda.synchronize(device)
+    host = np.ascontiguousarray(rows.cpu().numpy()).view(dt).reshape(n)
+    os.makedirs(path, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    np.save(os.path.join(path, prefix + "frame_index.npy"), idx.astype(np.float64))
+    for name in dt.names:
+        np.save(os.path.join(path, f"{prefix}{name}.npy"), host[name].astype(np.float64))
+    log(f"bench: wrote {len(dt.names) + 1} arrays of {n} of {count} frames to {path}")
+
+
 def timed(step, steps, warmup, stream, device, host_clock=False, with_local=False, stats=None):
     """W untimed steps (continued until WARMUP_SECONDS have passed), then
     exactly K steps bracketed by barrier + sync on both sides
@@ -590,7 +643,19 @@ def main():
     ap.add_argument("--lib", default=None,
                     help="another build of libnexg.so (A/B tools: nex_amd/libnexg_knobs.so reads the "
                          "measurement overrides NEXG_TILE_ORDER etc. from the environment)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the CPU baselines, the stream ceilings and other output "
+                         "kinds, the IMIX / malformed / real-traffic / 52M-frame / serialize objects and "
+                         "the span-clock and latency probes (the --no-* options switch parts of it off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy "
+                         "(a fixed seeded sample of the frames of a large batch; see dump_outputs)")
     args = ap.parse_args()
+    if args.dump_outputs and args.e2e:
+        ap.error("--dump-outputs covers the device-resident workloads, not --e2e")
+    if not args.full:  # a plain run measures the headline alone
+        args.no_imix = args.no_malformed = args.no_real = args.no_large = args.no_ser = True
+        args.no_cpu_baseline = True
     if args.lib:
         from nex_amd import _lib
         _lib.LIB_PATH = os.path.abspath(args.lib)
@@ -714,8 +779,11 @@ def main():
     with clocks.Sampler(device.index) as smp:
         elapsed, kernel_s, local_s = timed(step, args.steps, warm, stream, device, host_clock=args.e2e,
                                            with_local=True, stats=wstats)
+    if args.dump_outputs:  # before anything else writes to `out`
+        dump_outputs(args.dump_outputs, eng, batch, out, out_kind, F, rank, world, stream, device)
+    # the span-clock and latency probes are launches of their own: --full
     head_clocks = object_clocks(eng, batch, smp, stream, device) if batch is not None and not args.e2e \
-        else {"sysfs": smp.summary()}
+        and args.full else {"sysfs": smp.summary()}
     tp = dist.throughput(F, alg_bytes, args.steps, elapsed, device)
     # each rank's kernel time and its own timed-region wall time (balance across GPUs)
     per_rank = {"kernel_ms": dist.all_ranks(round(kernel_s * 1e3, 4), device),
@@ -723,7 +791,7 @@ def main():
     ceilings = None
     if args.workload == "udp64" and not args.e2e and not args.no_imix:
         ceilings = stream_ceilings(eng, batch, args, stream, device)
-    elif args.workload == "ser":
+    elif args.workload == "ser" and args.full:
         ceilings = write_ceiling(eng, out, args, stream, device)
     imix = None
     if args.workload == "udp64" and not args.e2e and not args.no_imix and F == 16 << 20:

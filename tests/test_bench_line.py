@@ -4,6 +4,7 @@
   line (18.8 KB, profiles/r05/s7/driver_cmd.log) shrinks below 7 KB with
   every object's roofline fraction, the contract's top-level fields whole,
   and the configs[2] IMIX / App. C mix / real-traffic objects printed last;
+- bench.dump_sample (--dump-outputs) picks the same frames in every run;
 - the product library reads no environment variable (the measurement
   overrides live only in nex_amd/libnexg_knobs.so);
 - the builders refuse per-frame arrays and outputs shorter than the batch
@@ -67,6 +68,20 @@ def test_shrink_keeps_every_frac_under_7kb():
     c = d["imix"]["clocks"]
     assert set(c) >= {"sclk_mhz", "mclk_mhz", "span_ghz", "span_share", "lat_ns"}
     assert len(c["span_share"]) == 5 and abs(sum(c["span_share"]) - 1) < 0.02
+
+
+def test_dump_sample_is_fixed_and_within_budget():
+    """--dump-outputs: a batch the budget holds is written whole; a larger one
+    as the same ascending sample of distinct frames in every run."""
+    import numpy as np
+
+    import bench
+    assert (bench.dump_sample(4096, 3) == np.arange(4096)).all()
+    for count, values in ((16 << 20, 3), (16 << 20, 30), (16 << 20, 42)):
+        a, b = bench.dump_sample(count, values), bench.dump_sample(count, values)
+        assert (a == b).all() and len(a) < count
+        assert (np.diff(a) > 0).all() and a[0] >= 0 and a[-1] < count
+        assert 0.9 * bench.DUMP_BUDGET < 8 * (values + 1) * len(a) <= bench.DUMP_BUDGET <= 64e6
 
 
 def test_product_library_reads_no_environment():

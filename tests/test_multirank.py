@@ -69,8 +69,11 @@ def _bench_worker(rank, world, port, q):
     MAX over ranks) + dist.throughput (SUM over ranks), the functions
     bench.py's timed() / main() call, on gloo."""
     import time
+    # a rank without a GPU, also where the suite runs on a GPU box: hide the
+    # devices before this fresh process makes its first HIP call
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank),
-                      MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+                      MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
+                      HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     import torch.distributed as tdist
     assert dist.pick_backend() == "gloo"  # no GPU in this process
     dist.init()

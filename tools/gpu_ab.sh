@@ -12,6 +12,6 @@ if [ -n "$BASE" ]; then
   rc=$?; echo "ab rc=$rc"; cat gpurun_out/ab.log | grep -v amdgpu.ids; [ $rc -ne 0 ] && exit $rc
 fi
 if [ -z "$NOBENCH" ]; then
-  timeout -k 10 600 python -u bench.py --steps 50 --cpu-seconds 5 > gpurun_out/bench.json 2> gpurun_out/bench.err
-  rc=$?; echo "bench rc=$rc"; cat gpurun_out/bench.json; exit $rc
+  timeout -k 10 600 python -u bench.py --full --steps 50 --cpu-seconds 5  # the line on stdout, its detail on stderr
+  rc=$?; echo "bench rc=$rc"; exit $rc
 fi

@@ -23,9 +23,9 @@ if [[ $STEPS == *pytest* || $STEPS == all ]]; then
   step pytest_gpu 900 python -u -m pytest tests -q -m gpu -x --timeout 120 --timeout-method thread
 fi
 if [[ $STEPS == *bench* || $STEPS == all ]]; then
-  step bench_udp64 400 python bench.py --steps 50 --warmup 5 --cpu-seconds 5
-  step bench_imix 400 python bench.py --workload imix --steps 20 --warmup 3 --cpu-seconds 5
-  step bench_ser 300 python bench.py --workload ser --steps 50 --warmup 5 --no-cpu-baseline
+  step bench_udp64 400 python bench.py --full --steps 50 --warmup 5 --cpu-seconds 5
+  step bench_imix 400 python bench.py --full --workload imix --steps 20 --warmup 3 --cpu-seconds 5
+  step bench_ser 300 python bench.py --full --workload ser --steps 50 --warmup 5 --no-cpu-baseline
   step bench_udp64_record 300 python bench.py --out record --steps 20 --warmup 3 --no-cpu-baseline
   step bench_imix_record 300 python bench.py --workload imix --out record --steps 10 --warmup 2 --no-cpu-baseline
 fi

@@ -12,7 +12,7 @@ step() {  # step <name> <seconds> <cmd...>
   if [ $rc -ne 0 ]; then echo "stopping at $name rc=$rc"; exit $rc; fi
 }
 step pytest_gpu 600 python -u -m pytest tests -x -q -m gpu --timeout 120 --timeout-method thread
-step bench_default 400 python bench.py
+step bench_default 400 python bench.py --full
 step bench_flags 300 python bench.py --out flags --no-cpu-baseline
 [ -x tools/kbench ] && step kbench 200 ./tools/kbench
 echo done

@@ -22,7 +22,7 @@ for s in ${STEPS:-tests}; do
     probewgs) step probe_wgs 900 bash -c 'for cfg in "0 def" "1 def" "1 0"; do set -- $cfg; export NEXG_PROBE_ICMP=$1; if [ $2 = 0 ]; then export NEXG_BUILD_LDS_PAD=0; fi; echo "cfg $cfg"; for l in nex_amd/libnexg.so abvar/libnexg_noprobe.so; do python tools/bench_builders.py --probe --lib $l || exit 1; done; done' ;;
        probetime) step probe_time 600 bash -c 'python -u tools/probe_timing.py --lib abvar/libnexg_ptime.so && NEXG_PROBE_WAVES=4 NEXG_PROBE_WGS=5 python -u tools/probe_timing.py --lib abvar/libnexg_ptime.so && python -u tools/probe_timing.py --lib abvar/libnexg_ptime_noprobe.so' ;;
     nodev) step nodev 600 bash -c 'for w in 1 4; do for l in nex_amd/libnexg.so abvar/libnexg_nodev.so; do NEXG_PROBE_WAVES=$w NEXG_PROBE_WGS=5 python tools/bench_builders.py --probe --lib $l || exit 1; done; done' ;;
-    mixprobe) step mix_probe 400 python3 bench.py --steps 20 --warmup 5 --no-large --no-ser --no-cpu-baseline ;;
+    mixprobe) step mix_probe 400 python3 bench.py --full --steps 20 --warmup 5 --no-large --no-ser --no-cpu-baseline ;;
     headab) step head_ab 600 python -u tools/bench_parse_ab.py --libs nex_amd/libnexg.so,abvar/libnexg_headlate.so --workloads imix,mix,real --out grouped --check --rounds 4 ;;
     r04ab) step r04_ab 900 env NEXG_AB_LIB_LENIENT=1 python -u tools/bench_parse_ab.py --libs nex_amd/libnexg.so,abvar/libnexg_head.so,abvar/libnexg_r04.so --workloads imix,mix,real --out grouped --check --rounds 4 ;;
     sparseab) step sparse_ab 600 env NEXG_AB_LIB_LENIENT=1 python -u tools/bench_parse_ab.py --libs nex_amd/libnexg.so,abvar/libnexg_head.so --workloads mix --out sparse --check --rounds 4 ;;
@@ -62,21 +62,21 @@ for s in ${STEPS:-tests}; do
     newtests) step pytest_new 600 python -u -m pytest tests/test_gpu_sparse.py tests/test_gpu_fixup.py -q -x --timeout 300 --timeout-method thread ;;
     tests) step pytest_gpu 900 python -u -m pytest tests -q -m gpu -x --timeout 300 --timeout-method thread ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) step bench_udp64 500 python bench.py --steps 50 --cpu-seconds 5 ;;
+    bench) step bench_udp64 500 python bench.py --full --steps 50 --cpu-seconds 5 ;;
     driverbench) step bench_driver 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 ;;
     malformedtests) step pytest_malformed 600 python -u -m pytest tests/test_gpu_malformed.py tests/test_gpu_span.py -q -x --timeout 300 --timeout-method thread ;;
     newtests4) step pytest_new4 600 python -u -m pytest tests/test_gpu_launch.py tests/test_gpu_tcp_options.py tests/test_gpu_build_probe.py "tests/test_gpu_parity.py::test_build_udp4_tuples_aos" tests/test_cpp_api.py -q -x --timeout 300 --timeout-method thread ;;
     malformed) step bench_malformed 500 python tools/bench_malformed.py ;;
-    benchpcap) step bench_pcap 400 python bench.py --workload imix_pcap --steps 20 --cpu-seconds 5 ;;
-    ser) step bench_ser 300 python bench.py --workload ser --steps 50 --no-cpu-baseline
-         step bench_ser_tuples 300 python bench.py --workload ser --ser-shape tuples --steps 50 --no-cpu-baseline
-         step bench_ser_aos 300 python bench.py --workload ser --ser-shape tuples_aos --steps 50 --no-cpu-baseline ;;
+    benchpcap) step bench_pcap 400 python bench.py --full --workload imix_pcap --steps 20 --cpu-seconds 5 ;;
+    ser) step bench_ser 300 python bench.py --full --workload ser --steps 50 --no-cpu-baseline
+         step bench_ser_tuples 300 python bench.py --full --workload ser --ser-shape tuples --steps 50 --no-cpu-baseline
+         step bench_ser_aos 300 python bench.py --full --workload ser --ser-shape tuples_aos --steps 50 --no-cpu-baseline ;;
     e2e) step bench_e2e 400 python bench.py --e2e --steps 5 --warmup 2 --no-cpu-baseline
          step bench_e2e_imix 400 python bench.py --e2e --workload imix --steps 3 --warmup 1 --no-cpu-baseline ;;
     # bench.py --gpus N starts its own N ranks (nex_amd/launch.py); gloo folds them onto the one GPU
-    rehearse2) step rehearse2 600 env NEXG_DIST_BACKEND=gloo python bench.py --gpus 2 --steps 20 --warmup 5 --cpu-seconds 2 ;;
-    rehearse8) step rehearse8 900 env NEXG_DIST_BACKEND=gloo python bench.py --gpus 8 --steps 10 --warmup 3 --cpu-seconds 2 --no-large ;;
-    benchimix) step bench_imix 400 python bench.py --workload imix --steps 20 --warmup 3 --cpu-seconds 5 ;;
+    rehearse2) step rehearse2 600 env NEXG_DIST_BACKEND=gloo python bench.py --full --gpus 2 --steps 20 --warmup 5 --cpu-seconds 2 ;;
+    rehearse8) step rehearse8 900 env NEXG_DIST_BACKEND=gloo python bench.py --full --gpus 8 --steps 10 --warmup 3 --cpu-seconds 2 --no-large ;;
+    benchimix) step bench_imix 400 python bench.py --full --workload imix --steps 20 --warmup 3 --cpu-seconds 5 ;;
     pmc) step pmc 900 bash tools/pmc.sh ;;
     sqkinds) step sqkinds 900 bash tools/sq_kinds.sh ;;
     tileorder) step tileorder 900 bash tools/tile_order_ab.sh ;;
@@ -131,8 +131,8 @@ for s in ${STEPS:-tests}; do
     offnt) step offnt_ab 900 python -u tools/bench_parse_ab.py --libs nex_amd/libnexg.so,abx/libnexg_vote.so --tables 32 --workloads imix,imix --out grouped --check --rounds 4 &&
         step offnt_ab2 900 python -u tools/bench_parse_ab.py --libs nex_amd/libnexg.so,abx/libnexg_vote.so --workloads real,mix --out grouped --check --rounds 4 ;;
     driverbench2) step bench_driver_2 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 && step bench_driver_3 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 ;;
-    # the driver's own command under the kernel trace: a row for every object of its line (tools/line_trace.py)
-    lineprof) step lineprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/lineprof -o run -- python3 bench.py --gpus 1 --steps 20 --warmup 5 ;;
+    # the driver's command with every object (--full) under the kernel trace, in $TRACES/lineprof: a row for each object of its line (tools/line_trace.py)
+    lineprof) step lineprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "${TRACES:-traces}/lineprof" -o run -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 ;;
     prof) step prof_udp64 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_udp64 -o run -- python3 bench.py --steps 60 --warmup 25 --no-cpu-baseline --no-imix --no-malformed --no-real --no-large --no-ser
           step prof_pcap 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_pcap -o run -- python3 bench.py --workload imix_pcap --steps 60 --warmup 25 --no-cpu-baseline
           step prof_imix 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_imix -o run -- python3 bench.py --workload imix --steps 60 --warmup 25 --no-cpu-baseline
