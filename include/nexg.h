@@ -531,6 +531,97 @@ typedef struct nexg_options {
 int nexg_decode_options(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records,
                         nexg_options* out, void* stream);
 
+/* ---- tunnel decapsulation (VXLAN, GRE) --------------------------------------
+ * Frame::try_from_buf stops at the outer UDP / IP header; the reference's
+ * tunnel parsers VxlanPacket::try_from_buf (vxlan.rs:28-65) and
+ * GrePacket::try_from_buf (gre.rs:32-107) read Frame.payload. Here a second
+ * pass over a batch already parsed with NEXG_OUT_RECORD (any parse option)
+ * locates each tunnel's inner frame inside the outer batch, with no copy of
+ * frame bytes: {frames->data, frames->data_bytes, inner_off, inner_len, count}
+ * is itself a valid nexg_frames table (offsets + lengths; monotone whenever
+ * the outer batch's offsets are nondecreasing), and nexg_decap_select compacts
+ * it by inner class into the tables nexg_parse_batch takes: inner Ethernet
+ * with the default option, inner IP with NEXG_PARSE_FROM_IP, ip_offset 0.
+ *
+ * Candidates (only the record's own fields decide):
+ *   VXLAN  NEXG_DECAP_VXLAN set; status 0, NEXG_L_UDP, dst_port == the VXLAN
+ *          port. Fewer than 8 payload bytes: kind VXLAN, status MALFORMED (the
+ *          reference returns None). The I flag is not looked at (nor does the
+ *          reference); flags reports the byte.
+ *   GRE    NEXG_DECAP_GRE set; status 0, NEXG_L_IPV4 or NEXG_L_IPV6, no
+ *          transport / ICMP / ICMPv6 layer, ip_proto == 47: Frame.payload is
+ *          the IP payload (frame.rs:466-468, 511-513). Fewer than 4 bytes, or
+ *          an optional 4-B field (checksum + offset when C or R, key when K,
+ *          sequence when S, in that order) cut short: MALFORMED; the routing
+ *          bit: MALFORMED once the other optional fields were consumed.
+ *          Version and zero flags are not checked (flags reports them). The
+ *          checksum and offset words stay readable at outer frame bytes
+ *          [payload_off + 4, payload_off + 8).
+ * An accepted tunnel (kind != 0, status 0) gets inner_off = off(i) +
+ * payload_off + hdr_len (absolute in frames->data) and inner_len =
+ * payload_len - hdr_len (may be 0). Every other frame (not a candidate,
+ * malformed tunnel, error status, bad extent) gets inner_off = off(i) (0 where
+ * off(i) is undefined), inner_len = 0, and every nexg_tunnel field not named
+ * above 0. Records are caller memory: one whose payload_off + payload_len
+ * exceeds len(i) makes its frame a non-candidate, and nothing outside the
+ * frame's own extent is read (the 16-B block rule of the frame batch layout
+ * applies). */
+#define NEXG_TUN_NONE 0
+#define NEXG_TUN_VXLAN 1
+#define NEXG_TUN_GRE 2
+#define NEXG_INNER_OTHER 0     /* not a frame this library parses */
+#define NEXG_INNER_ETHERNET 1  /* VXLAN; GRE protocol_type 0x6558 */
+#define NEXG_INNER_IPV4 2      /* GRE protocol_type 0x0800 */
+#define NEXG_INNER_IPV6 3      /* GRE protocol_type 0x86DD */
+#define NEXG_DECAP_VXLAN 0x1u
+#define NEXG_DECAP_GRE 0x2u
+typedef struct nexg_decap_option {
+    uint32_t which;       /* NEXG_DECAP_* */
+    uint16_t vxlan_port;  /* UDP destination port; 0 means 4789 */
+    uint16_t reserved;    /* must be 0 */
+} nexg_decap_option;
+typedef struct nexg_tunnel {  /* 16 bytes */
+    uint8_t kind;     /* NEXG_TUN_* */
+    uint8_t status;   /* NEXG_FRAME_OK, or NEXG_ERR_MALFORMED where the reference's try_from_buf returns None */
+    uint8_t inner;    /* NEXG_INNER_* */
+    uint8_t hdr_len;  /* VXLAN 8; GRE 4 + 4*(C|R) + 4*K + 4*S */
+    uint16_t flags;   /* VXLAN: the flags byte; GRE: the first 16 bits as read */
+    uint16_t proto;   /* GRE protocol_type; VXLAN 0 */
+    uint32_t id;      /* VXLAN vni (24 bits); GRE key, 0 if absent */
+    uint32_t aux;     /* VXLAN reserved1 << 8 | reserved2; GRE sequence, 0 if absent */
+} nexg_tunnel;
+
+/* records[i] = frame i's record from a NEXG_OUT_RECORD parse of the same
+ * batch (16-B aligned). option NULL = both tunnel kinds, port 4789. Outputs
+ * hold `count` entries: tunnels 16-B, inner_off 8-B, inner_len 4-B aligned.
+ * NEXG_EINVAL: a NULL pointer with count > 0, reserved != 0, unknown `which`
+ * bits, a misaligned output. count == 0 launches nothing. Device pointers,
+ * stream-ordered. */
+int nexg_decap_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records,
+                     const nexg_decap_option* option, nexg_tunnel* tunnels,
+                     uint64_t* inner_off, uint32_t* inner_len, void* stream);
+
+/* Order-preserving compaction of a decap result by inner class: frame i is
+ * selected when tunnels[i].status == 0, tunnels[i].kind != 0 and
+ * inner_mask & (1u << tunnels[i].inner) is nonzero. For the k-th selected
+ * frame in index order out_index[k] = i, out_off[k] = inner_off[i],
+ * out_len[k] = inner_len[i]; *out_count (device memory, 8-B aligned) = the
+ * number selected. The output arrays have capacity `count`; count must not
+ * exceed 2^32 - 1 (NEXG_EINVAL). workspace: caller-owned device memory (4-B
+ * aligned) of at least the bytes the helper below gives (NEXG_EINVAL when
+ * smaller): one u32 counter per 256-frame tile, turned into the tiles'
+ * exclusive scan in place. Deterministic: ballots and scans decide positions,
+ * no atomics. Three kernels on `stream`. */
+int nexg_decap_select(nexg_ctx* ctx, const nexg_tunnel* tunnels, const uint64_t* inner_off,
+                      const uint32_t* inner_len, uint64_t count, uint32_t inner_mask,
+                      uint32_t* out_index, uint64_t* out_off, uint32_t* out_len,
+                      uint64_t* out_count, void* workspace, uint64_t workspace_bytes, void* stream);
+/* one u32 per 256-frame tile, rounded up to whole 256-tile scan chunks, + 16 B */
+static inline uint64_t nexg_decap_select_workspace(uint64_t count) {
+    const uint64_t tiles = (count + 255u) / 256u;
+    return 4u * ((tiles + 255u) / 256u * 256u) + 16u;
+}
+
 /* ---- calibration (not a reference entry point) ---------------------------
  * The HBM stream ceilings the parse kernels are measured against, on the
  * caller's own buffer and box: `bytes` (a multiple of 16384) read with the

@@ -858,6 +858,69 @@ class Engine {  // one nexg context on one gfx950 device, one stream
         check(nexg_parse_batch(ctx_, &frames, &o, out_kind, out, stream_), "nexg_parse_batch");
     }
 
+    // Tunnel decapsulation of a device-resident batch already parsed with
+    // NEXG_OUT_RECORD (VxlanPacket::try_from_buf vxlan.rs:28-65,
+    // GrePacket::try_from_buf gre.rs:32-107 on Frame.payload): tunnels /
+    // inner_off / inner_len are device arrays of frames.count entries;
+    // {frames.data, frames.data_bytes, inner_off, inner_len} is the inner batch
+    void decap(const nexg_frames& frames, const nexg_record* records, nexg_tunnel* tunnels, uint64_t* inner_off,
+               uint32_t* inner_len, uint32_t which = NEXG_DECAP_VXLAN | NEXG_DECAP_GRE, uint16_t vxlan_port = 4789) {
+        DeviceScope ds(device_);
+        const nexg_decap_option o{which, vxlan_port, 0};
+        check(nexg_decap_batch(ctx_, &frames, records, &o, tunnels, inner_off, inner_len, stream_), "nexg_decap_batch");
+    }
+
+    // Order-preserving compaction of a decap result by inner class
+    // (inner_mask: bits 1u << NEXG_INNER_*): device arrays of capacity `count`;
+    // returns the number selected (one stream synchronisation). Parse the
+    // selected table with the default option for NEXG_INNER_ETHERNET, with
+    // ParseOption{from_ip_packet = true, offset = 0} for the IP classes.
+    uint64_t decap_select(const nexg_tunnel* tunnels, const uint64_t* inner_off, const uint32_t* inner_len,
+                          uint64_t count, uint32_t inner_mask, uint32_t* out_index, uint64_t* out_off,
+                          uint32_t* out_len) {
+        DeviceScope ds(device_);
+        const uint64_t wsb = nexg_decap_select_workspace(count);
+        void* ws = scratch(16, wsb);
+        uint64_t* d_count = static_cast<uint64_t*>(scratch(17, 8));
+        check(nexg_decap_select(ctx_, tunnels, inner_off, inner_len, count, inner_mask, out_index, out_off, out_len,
+                                d_count, ws, wsb, stream_),
+              "nexg_decap_select");
+        uint64_t k = 0;
+        check_hip(hipMemcpyAsync(&k, d_count, 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        return k;
+    }
+
+    // The tunnel of every host frame: parse (NEXG_OUT_RECORD) + decap on the
+    // device; inner_off is relative to the frame's first byte
+    struct Decap {
+        nexg_tunnel tunnel;
+        uint32_t inner_off, inner_len;
+    };
+    std::vector<Decap> decap_bufs(const std::vector<std::vector<uint8_t>>& frames, ParseOption option = {},
+                                  uint32_t which = NEXG_DECAP_VXLAN | NEXG_DECAP_GRE, uint16_t vxlan_port = 4789) {
+        DeviceScope ds(device_);
+        const uint64_t n = frames.size();
+        std::vector<Decap> out(n);
+        if (n == 0) return out;
+        HostBatch hb(*this, frames);
+        void* d_recs = scratch(3, n * 64);
+        nexg_tunnel* d_tun = static_cast<nexg_tunnel*>(scratch(4, n * sizeof(nexg_tunnel)));
+        uint64_t* d_off = static_cast<uint64_t*>(scratch(5, n * 8));
+        uint32_t* d_len = static_cast<uint32_t*>(scratch(6, n * 4));
+        parse(hb.fb, option, ParseMode::Lenient, NEXG_OUT_RECORD, d_recs);
+        decap(hb.fb, static_cast<const nexg_record*>(d_recs), d_tun, d_off, d_len, which, vxlan_port);
+        std::vector<nexg_tunnel> tun(n);
+        std::vector<uint64_t> off(n);
+        std::vector<uint32_t> len(n);
+        check_hip(hipMemcpyAsync(tun.data(), d_tun, n * sizeof(nexg_tunnel), hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipMemcpyAsync(off.data(), d_off, n * 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipMemcpyAsync(len.data(), d_len, n * 4, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        for (uint64_t i = 0; i < n; i++) out[i] = Decap{tun[i], (uint32_t)(off[i] - hb.offs[i]), len[i]};
+        return out;
+    }
+
     // Frame::try_from_buf_with_mode (frame.rs:309) on every host frame: the
     // batch is packed, copied to the device, parsed (NEXG_OUT_RECORD), its
     // option lists decoded, and each Frame materialised from its record.

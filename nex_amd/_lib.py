@@ -49,6 +49,8 @@ def load():
         "nexg_probe_span_clock": (I, [P, ctypes.POINTER(abi.Frames), ctypes.POINTER(abi.ParseOptionC), P, P, P]),
         "nexg_probe_latency": (I, [P, P, U64, U32, U32, U32, P, P]),
         "nexg_decode_options": (I, [P, ctypes.POINTER(abi.Frames), P, P, P]),
+        "nexg_decap_batch": (I, [P, ctypes.POINTER(abi.Frames), P, ctypes.POINTER(abi.DecapOption), P, P, P, P]),
+        "nexg_decap_select": (I, [P, P, P, P, U64, U32, P, P, P, P, P, U64, P]),
         "nexg_build_udp4_batch": (I, [P, ctypes.POINTER(abi.Udp4Build), P, U32, P]),
         "nexg_build_udp4_tuples": (I, [P, ctypes.POINTER(abi.Udp4Build), P, P, U32, P]),
         "nexg_build_udp6_batch": (I, [P, ctypes.POINTER(abi.Udp6Build), P, U32, P]),

@@ -391,14 +391,37 @@ FIXUP_DTYPE = np.dtype([("done", "u1"), ("proto", "u1"), ("ip_csum", "<u2"), ("l
                         ("l4_off", "<u2")])
 assert FIXUP_DTYPE.itemsize == 8
 
+# tunnel decapsulation (nexg_decap_batch / nexg_decap_select)
+TUN_NONE, TUN_VXLAN, TUN_GRE = 0, 1, 2
+INNER_OTHER, INNER_ETHERNET, INNER_IPV4, INNER_IPV6 = 0, 1, 2, 3
+DECAP_VXLAN = 0x1
+DECAP_GRE = 0x2
+VXLAN_PORT = 4789  # what nexg_decap_option.vxlan_port = 0 means
+TUNNEL_DTYPE = np.dtype([("kind", "u1"), ("status", "u1"), ("inner", "u1"), ("hdr_len", "u1"), ("flags", "<u2"),
+                         ("proto", "<u2"), ("id", "<u4"), ("aux", "<u4")])
+assert TUNNEL_DTYPE.itemsize == 16
+
+
+class DecapOption(ctypes.Structure):
+    """struct nexg_decap_option"""
+    _fields_ = [("which", ctypes.c_uint32), ("vxlan_port", ctypes.c_uint16), ("reserved", ctypes.c_uint16)]
+
+
+def decap_select_workspace(count):
+    """nexg_decap_select_workspace: bytes of nexg_decap_select's workspace."""
+    tiles = (int(count) + 255) // 256
+    return 4 * ((tiles + 255) // 256 * 256) + 16
+
+
 #: static inline helpers of include/nexg.h (header-only, not exported)
 HEADER_INLINE = ("nexg_sparse_decode", "nexg_grouped_code", "nexg_grouped_exc_slot", "nexg_offsets32_bases",
-                 "nexg_offsets32_bytes")
+                 "nexg_offsets32_bytes", "nexg_decap_select_workspace")
 
 #: every symbol include/nexg.h declares (tests check the .so exports them)
 EXPORTED_SYMBOLS = (
     "nexg_abi_version", "nexg_strerror", "nexg_ctx_create", "nexg_ctx_destroy",
     "nexg_ctx_last_error", "nexg_ctx_cu_count", "nexg_parse_batch", "nexg_checksum_batch", "nexg_decode_options", "nexg_probe_stream",
+    "nexg_decap_batch", "nexg_decap_select",
     "nexg_probe_span_clock", "nexg_probe_latency",
     "nexg_sparse_expand", "nexg_grouped_expand", "nexg_recompute_checksums_batch",
     "nexg_rx_config_default", "nexg_rx_open", "nexg_rx_next_batch", "nexg_rx_stats", "nexg_rx_close",

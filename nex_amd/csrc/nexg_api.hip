@@ -253,6 +253,55 @@ int nexg_decode_options(nexg_ctx* ctx, const nexg_frames* frames, const nexg_rec
                       NEXG_ELAUNCH);
 }
 
+int nexg_decap_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records,
+                     const nexg_decap_option* option, nexg_tunnel* tunnels, uint64_t* inner_off,
+                     uint32_t* inner_len, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    uint32_t which = NEXG_DECAP_VXLAN | NEXG_DECAP_GRE, port = 4789u;
+    if (option) {
+        if (option->reserved != 0) return fail(ctx, NEXG_EINVAL, "decap option: reserved must be 0%s", nullptr);
+        if ((option->which & ~(NEXG_DECAP_VXLAN | NEXG_DECAP_GRE)) != 0)
+            return fail(ctx, NEXG_EINVAL, "decap option: unknown tunnel kind bits%s", nullptr);
+        which = option->which;
+        if (option->vxlan_port) port = option->vxlan_port;
+    }
+    if (frames->count && (!records || !tunnels || !inner_off || !inner_len))
+        return fail(ctx, NEXG_EINVAL, "NULL records or output%s", nullptr);
+    if ((reinterpret_cast<uint64_t>(records) & 15u) != 0 || (reinterpret_cast<uint64_t>(tunnels) & 15u) != 0 ||
+        (reinterpret_cast<uint64_t>(inner_off) & 7u) != 0 || (reinterpret_cast<uint64_t>(inner_len) & 3u) != 0)
+        return fail(ctx, NEXG_EINVAL, "misaligned records or output%s", nullptr);
+    const nexg::ParseArgs a = to_args(frames);
+    DeviceGuard g(ctx);
+    return hip_status(ctx, nexg::launch_decap(a, records, which, port, tunnels, inner_off, inner_len,
+                                              static_cast<hipStream_t>(stream)),
+                      NEXG_ELAUNCH);
+}
+
+int nexg_decap_select(nexg_ctx* ctx, const nexg_tunnel* tunnels, const uint64_t* inner_off,
+                      const uint32_t* inner_len, uint64_t count, uint32_t inner_mask, uint32_t* out_index,
+                      uint64_t* out_off, uint32_t* out_len, uint64_t* out_count, void* workspace,
+                      uint64_t workspace_bytes, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "decap_select: more than 2^32 - 1 frames%s", nullptr);
+    if (!out_count) return fail(ctx, NEXG_EINVAL, "NULL out_count%s", nullptr);
+    if (count && (!tunnels || !inner_off || !inner_len || !out_index || !out_off || !out_len || !workspace))
+        return fail(ctx, NEXG_EINVAL, "NULL input, output or workspace%s", nullptr);
+    if (count && workspace_bytes < nexg_decap_select_workspace(count))
+        return fail(ctx, NEXG_EINVAL, "decap_select: workspace smaller than nexg_decap_select_workspace%s", nullptr);
+    if ((reinterpret_cast<uint64_t>(tunnels) & 15u) != 0 ||
+        ((reinterpret_cast<uint64_t>(inner_off) | reinterpret_cast<uint64_t>(out_off) |
+          reinterpret_cast<uint64_t>(out_count)) & 7u) != 0 ||
+        ((reinterpret_cast<uint64_t>(inner_len) | reinterpret_cast<uint64_t>(out_index) |
+          reinterpret_cast<uint64_t>(out_len) | reinterpret_cast<uint64_t>(workspace)) & 3u) != 0)
+        return fail(ctx, NEXG_EINVAL, "misaligned input, output or workspace%s", nullptr);
+    DeviceGuard g(ctx);
+    return hip_status(ctx, nexg::launch_decap_select(tunnels, inner_off, inner_len, count, inner_mask, out_index,
+                                                     out_off, out_len, out_count, static_cast<uint32_t*>(workspace),
+                                                     static_cast<hipStream_t>(stream)),
+                      NEXG_ELAUNCH);
+}
+
 int nexg_probe_stream(nexg_ctx* ctx, const void* data, uint64_t bytes, uint32_t out_per_64,
                       void* out, void* stream) {
     if (!ctx) return NEXG_EINVAL;

@@ -101,6 +101,15 @@ hipError_t launch_recompute(const ParseArgs& a, uint32_t which, nexg_fixup* out,
 hipError_t launch_decode_options(const ParseArgs& a, const nexg_record* recs, nexg_options* out,
                                  hipStream_t s);
 
+// nexg_decap_batch / nexg_decap_select (nexg_decap.hip). tile_count: one u32
+// per 256-frame tile (the caller's workspace), left holding the tiles'
+// exclusive scan.
+hipError_t launch_decap(const ParseArgs& a, const nexg_record* recs, uint32_t which, uint32_t vxlan_port,
+                        nexg_tunnel* tunnels, uint64_t* inner_off, uint32_t* inner_len, hipStream_t s);
+hipError_t launch_decap_select(const nexg_tunnel* tunnels, const uint64_t* inner_off, const uint32_t* inner_len,
+                               uint64_t count, uint32_t inner_mask, uint32_t* out_index, uint64_t* out_off,
+                               uint32_t* out_len, uint64_t* out_count, uint32_t* tile_count, hipStream_t s);
+
 hipError_t launch_probe_stream(const uint8_t* data, uint64_t tiles, uint32_t mode, void* out, hipStream_t s);
 hipError_t launch_probe_latency(uint32_t* buf, uint32_t lines, uint32_t start, uint32_t steps, uint32_t loaded_wgs,
                                 uint32_t rounds, uint64_t* out, hipStream_t s);

@@ -275,6 +275,71 @@ class Engine:
                                                  self._stream(stream)))
         return out
 
+    def decap(self, batch: FrameBatch, records, which: int = abi.DECAP_VXLAN | abi.DECAP_GRE,
+              vxlan_port: int = abi.VXLAN_PORT, stream=None):
+        """Locate every VXLAN / GRE tunnel's inner frame inside `batch`
+        (nexg_decap_batch; VxlanPacket::try_from_buf vxlan.rs:28-65,
+        GrePacket::try_from_buf gre.rs:32-107 on Frame.payload). `records` is
+        the uint8 device tensor a NEXG_OUT_RECORD parse of `batch` returned
+        (any parse option). Returns (tunnels, inner): tunnels a uint8 device
+        tensor holding nexg_tunnel[count] (abi.TUNNEL_DTYPE), inner a
+        FrameBatch of `count` frames that shares batch.data (no bytes are
+        copied) with the inner offsets + lengths; frames that are no accepted
+        tunnel have length 0. inner carries FRAMES_MONOTONE exactly when the
+        outer batch is fixed-stride, packed or itself monotone.
+
+        The two-call recipe for the inner frames:
+
+            tunnels, inner = eng.decap(batch, records)
+            idx, eth = eng.decap_select(tunnels, inner, {abi.INNER_ETHERNET})
+            rec_eth = eng.parse(eth, out_kind=abi.OUT_RECORD)
+            idx, ip = eng.decap_select(tunnels, inner, {abi.INNER_IPV4, abi.INNER_IPV6})
+            rec_ip = eng.parse(ip, ParseOption(from_ip_packet=True, offset=0), out_kind=abi.OUT_RECORD)
+
+        idx[k] is the outer frame of the k-th selected inner frame."""
+        torch = _torch()
+        n = max(batch.count, 1)
+        tunnels = torch.empty(n * 16, dtype=torch.uint8, device=self.torch_device)
+        off = torch.empty(n, dtype=torch.int64, device=self.torch_device)
+        ln = torch.empty(n, dtype=torch.int32, device=self.torch_device)
+        fr = batch.to_c()
+        opt = abi.DecapOption(which, vxlan_port, 0)
+        self._check(self.lib.nexg_decap_batch(self.ctx, ctypes.byref(fr), _ptr(records), ctypes.byref(opt),
+                                              _ptr(tunnels), _ptr(off), _ptr(ln), self._stream(stream)))
+        ordered = batch.offsets is None or batch.lengths is None or bool(batch.hints & abi.FRAMES_MONOTONE)
+        inner = FrameBatch(data=batch.data, count=batch.count, offsets=off[: batch.count], lengths=ln[: batch.count],
+                           hints=abi.FRAMES_MONOTONE if ordered else 0)
+        return tunnels[: batch.count * 16], inner
+
+    def decap_select(self, tunnels, inner: FrameBatch, classes, stream=None):
+        """Order-preserving compaction of a decap result (nexg_decap_select):
+        the accepted tunnels whose inner class (abi.INNER_*) is in `classes`.
+        Returns (index, batch): index an int32 device tensor (bit patterns of
+        u32) with the outer frame number of each selected inner frame, batch a
+        FrameBatch over the same data whose count is the selected count, ready
+        for Engine.parse: {INNER_ETHERNET} with the default option,
+        {INNER_IPV4, INNER_IPV6} with ParseOption(from_ip_packet=True,
+        offset=0) (see Engine.decap). Allocates the workspace and reads the
+        selected count back: one synchronisation of the stream."""
+        torch = _torch()
+        mask = 0
+        for c in classes:
+            mask |= 1 << int(c)
+        count = inner.count
+        n = max(count, 1)
+        dev = self.torch_device
+        idx = torch.empty(n, dtype=torch.int32, device=dev)
+        off = torch.empty(n, dtype=torch.int64, device=dev)
+        ln = torch.empty(n, dtype=torch.int32, device=dev)
+        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        ws_bytes = abi.decap_select_workspace(count)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        self._check(self.lib.nexg_decap_select(self.ctx, _ptr(tunnels), _ptr(inner.offsets), _ptr(inner.lengths), count,
+                                               mask, _ptr(idx), _ptr(off), _ptr(ln), _ptr(cnt), _ptr(ws), ws_bytes,
+                                               self._stream(stream)))
+        k = int(cnt.item())  # waits for the kernels
+        return idx[:k], FrameBatch(data=inner.data, count=k, offsets=off[:k], lengths=ln[:k], hints=inner.hints)
+
     def probe_stream(self, data, write8, out=None, stream=None):
         """Calibration stream over a uint8 device tensor (nexg_probe_stream):
         the parse kernels' load shape, read-only or with the 8-B-per-64-B
