@@ -622,6 +622,113 @@ static inline uint64_t nexg_decap_select_workspace(uint64_t count) {
     return 4u * ((tiles + 255u) / 256u * 256u) + 16u;
 }
 
+/* ---- DNS messages ------------------------------------------------------------
+ * Frame::try_from_buf stops at the UDP header; the reference's DNS parser
+ * DnsPacket::try_from_buf (dns.rs:1166-1259) reads Frame.payload, as its
+ * example caller does (dns_dump.rs:97-101). Here a second pass over a batch
+ * already parsed with NEXG_OUT_RECORD (any parse option) walks each DNS
+ * message in place: nexg_dns_batch writes one nexg_dns summary per frame and
+ * the prefix sums that place a variable number of entries per frame;
+ * nexg_dns_entries walks again and writes one nexg_dns_entry per query and
+ * resource record. Names are not decoded on the device: an entry gives the
+ * offsets at which a host decoder (decode_dns_name, dns.rs:1303-1390) starts.
+ *
+ * Candidates (only the record's own fields decide): status 0, NEXG_L_UDP,
+ * payload_len > 0, payload_off + payload_len <= len(i), and src_port == port
+ * or dst_port == port, or NEXG_DNS_ANY_UDP (dns_dump.rs:98-100 tries every
+ * UDP payload that is not empty). A non-candidate (bad extent included) gets
+ * an all-zero nexg_dns but for `first`.
+ *
+ * A candidate's message M of n = payload_len bytes, as dns.rs:1166-1259 with
+ * DnsQueryPacket::from_buf_mut (dns.rs:752-790) and
+ * DnsResponsePacket::from_buf_mut (dns.rs:904-945):
+ *   n < 12: status NEXG_ERR_BUFFER_TOO_SHORT (dns.rs:1167-1173), every other
+ *     field 0 (flags8 too), no entries.
+ *   Header bytes 0..11 give id, flags, qd, an, ns, ar; pos = 12.
+ *   Each of qd queries: labels until a zero length byte; a length byte L is a
+ *     plain length whatever its top bits (0xC0..0xFF are NOT compression
+ *     pointers here, dns.rs:759-769); pos >= n before a length byte, n - pos < L
+ *     after one, or n - pos < 4 after the zero byte fail the whole message
+ *     (dns.rs:1228-1231, "DNS query section"): status NEXG_ERR_MALFORMED;
+ *     flags8 bit 0, msg_off, msg_len, id, flags, qd, an, ns, ar are kept,
+ *     n_*, rest_off are 0 and there are no entries.
+ *   Then an, ns, ar records: a section stops silently when n - pos < 12
+ *     (dns.rs:905-907, 1213-1221), and since the cursor does not move every
+ *     later section then parses 0 records too; flags8 bit 1 is set when fewer
+ *     records were parsed than declared. A record is always name_tag u16,
+ *     type, class, ttl u32, data_len (an uncompressed owner name is read as
+ *     these 12 bytes all the same) and pos advances by
+ *     12 + min(n - pos - 12, data_len) (dns.rs:929-931).
+ *   rest_off = pos at the end: DnsPacket.payload is M[rest_off, n).
+ *
+ * Entries follow message order (queries, answers, authorities, additionals).
+ * With T = ceil(count / 256) tiles, tile_first has T + 1 elements (device
+ * memory, 8-B aligned): tile_first[t] = the number of entries of frames
+ * [0, 256 t), tile_first[T] = the batch total. The k-th entry of frame i has
+ * index tile_first[i >> 8] + dns[i].first + k. Positions come from scans
+ * alone (no atomics): the output is the same on every run.
+ *
+ * Query fields: type and class at M[off + name .. + 4), the qname bytes are
+ * M[off, off + name). Record data: M[off + 12, off + 12 + min(data_len,
+ * msg_len - off - 12)).
+ *
+ * Records, summaries and tile_first are caller memory: nothing outside a
+ * frame's own extent is read (msg_off + msg_len is clamped to it and every
+ * bound is re-checked from the bytes), and nexg_dns_entries stores nothing at
+ * or past entries_cap, whatever the summaries hold. */
+#define NEXG_DNS_ANY_UDP 0x1u /* dns_dump.rs:98-100: try every UDP frame with a non-empty payload */
+typedef struct nexg_dns_option {
+    uint32_t flags;    /* NEXG_DNS_*; unknown bits -> NEXG_EINVAL */
+    uint16_t port;     /* UDP source OR destination port; 0 means 53 */
+    uint16_t reserved; /* must be 0 */
+} nexg_dns_option;
+typedef struct nexg_dns { /* 32 bytes per frame */
+    uint8_t status;    /* NEXG_FRAME_OK | NEXG_ERR_BUFFER_TOO_SHORT (< 12 B, dns.rs:1167-1173)
+                          | NEXG_ERR_MALFORMED ("DNS query section", dns.rs:1228-1231) */
+    uint8_t flags8;    /* bit 0 candidate (with at least 12 bytes); bit 1 a record section ended early */
+    uint16_t msg_off;  /* frame-relative offset of the DNS message (= record payload_off) */
+    uint16_t msg_len;  /* = record payload_len */
+    uint16_t id;
+    uint16_t flags;    /* header bytes 2..3 as a BE value (QR, opcode, AA, TC, RD, RA, Z, AD, CD, rcode) */
+    uint16_t qd, an, ns, ar;        /* declared counts, header bytes 4..11 */
+    uint16_t n_q, n_an, n_ns, n_ar; /* queries.len(), responses.len(), authorities.len(), additionals.len() */
+    uint16_t rest_off; /* message-relative offset of DnsPacket.payload; its length = msg_len - rest_off */
+    uint32_t first;    /* entries of this frame's tile before this frame (see tile_first) */
+} nexg_dns;
+typedef struct nexg_dns_entry { /* 16 bytes per query / resource record */
+    uint8_t section;    /* 0 query, 1 answer, 2 authority, 3 additional */
+    uint8_t flags8;     /* bit 0: record data cut short (safe_data_len < data_len, dns.rs:929) */
+    uint16_t off;       /* message-relative offset of the entry's first byte */
+    uint16_t type;      /* qtype / rtype value */
+    uint16_t dns_class; /* qclass / rclass value */
+    uint32_t ttl;       /* record ttl; query 0 */
+    uint16_t name;      /* query: qname.len() including the zero byte; record: name_tag */
+    uint16_t data_len;  /* record: declared data_len; query 0 */
+} nexg_dns_entry;
+
+/* ceil(count / 256) + 1 u64 elements */
+static inline uint64_t nexg_dns_tile_first_bytes(uint64_t count) { return 8u * ((count + 255u) / 256u + 1u); }
+
+/* records[i] = frame i's record from a NEXG_OUT_RECORD parse of the same
+ * batch (16-B aligned). option NULL = port 53, no flags. `out` holds `count`
+ * summaries (16-B aligned), tile_first the bytes the helper above gives (8-B
+ * aligned). NEXG_EINVAL: a NULL pointer with count > 0, reserved != 0, unknown
+ * flag bits, a misaligned output, count > 2^32 - 1. count == 0 writes
+ * tile_first[0] = 0 and nothing else. Two kernels on `stream`. Device
+ * pointers, stream-ordered. */
+int nexg_dns_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records,
+                   const nexg_dns_option* option, nexg_dns* out, uint64_t* tile_first, void* stream);
+
+/* One entry per query / resource record of every frame whose summary is a
+ * candidate with status 0, at tile_first[i >> 8] + dns[i].first + k; entry
+ * indices at or past entries_cap are not written (the batch total is
+ * tile_first's last element). At most n_q + n_an + n_ns + n_ar entries per
+ * frame. entries: 16-B aligned; NULL with entries_cap 0 is valid and launches
+ * nothing. NEXG_EINVAL: a NULL pointer with count > 0, NULL entries with a
+ * nonzero capacity, a misaligned pointer, count > 2^32 - 1. */
+int nexg_dns_entries(nexg_ctx* ctx, const nexg_frames* frames, const nexg_dns* dns,
+                     const uint64_t* tile_first, nexg_dns_entry* entries, uint64_t entries_cap, void* stream);
+
 /* ---- calibration (not a reference entry point) ---------------------------
  * The HBM stream ceilings the parse kernels are measured against, on the
  * caller's own buffer and box: `bytes` (a multiple of 16384) read with the

@@ -20,6 +20,9 @@
  *                           tuple, Result<frames, BuildError>
  *   Engine::build_tcp_ping / build_icmp_ping   tcp_ping.rs:111-163 /
  *                           icmp_ping.rs:67-102 (IPv4 or IPv6 per batch)
+ *   Engine::dns / dns_entries / dns_bufs   DnsPacket::try_from_buf
+ *                           (dns.rs:1166-1259) on every UDP payload of a batch;
+ *                           decode_dns_name   dns.rs:1303-1390 (on the host)
  * The device does the parse and the checksums (nexg_parse_batch,
  * NEXG_OUT_RECORD) and the option lists (nexg_decode_options); this header
  * only reads header fields out of the frame bytes at the offsets the device
@@ -128,6 +131,78 @@ class Result {
 struct Error : std::runtime_error {
     using std::runtime_error::runtime_error;
 };
+
+/* ---- DNS names ---------------------------------------------------------- */
+
+// A decoded DNS name and the bytes it took at `start`
+struct DnsNameDecoded {
+    std::string name;
+    size_t consumed = 0;
+};
+
+// decode_dns_name (dns.rs:1303-1390) over buf[0, n) from `start`: labels
+// joined with '.', compression pointers followed inside buf (a target seen
+// before, or more than 16 jumps: CompressionLoop; a target at or past n:
+// InvalidCompression), label types 0x40 / 0x80 InvalidCompression, labels
+// checked as UTF-8. The error is the ParseError variant's name. Names are
+// decoded on the host from the offsets the nexg_dns_entry rows carry
+// (Engine::dns / dns_entries): a query's over its qname bytes alone.
+inline Result<DnsNameDecoded, const char*> decode_dns_name(const uint8_t* buf, size_t n, size_t start = 0) {
+    auto utf8 = [](const uint8_t* p, size_t len) {  // what str::from_utf8 accepts
+        for (size_t i = 0; i < len;) {
+            const uint8_t c = p[i];
+            size_t k;
+            uint32_t cp;
+            if (c < 0x80) { i++; continue; }
+            if (c >= 0xC2 && c <= 0xDF) k = 1, cp = c & 0x1Fu;
+            else if (c >= 0xE0 && c <= 0xEF) k = 2, cp = c & 0x0Fu;
+            else if (c >= 0xF0 && c <= 0xF4) k = 3, cp = c & 0x07u;
+            else return false;
+            if (i + k >= len) return false;
+            for (size_t j = 1; j <= k; j++) {
+                if ((p[i + j] & 0xC0) != 0x80) return false;
+                cp = (cp << 6) | (p[i + j] & 0x3Fu);
+            }
+            if ((k == 2 && (cp < 0x800 || (cp >= 0xD800 && cp <= 0xDFFF))) || (k == 3 && (cp < 0x10000 || cp > 0x10FFFF)))
+                return false;
+            i += k + 1;
+        }
+        return true;
+    };
+    DnsNameDecoded out;
+    std::vector<size_t> visited;
+    size_t pos = start, depth = 0;
+    bool jumped = false, first = true;
+    for (;;) {
+        if (pos >= n) return "Truncated";
+        const uint8_t len = buf[pos];
+        if (!jumped) out.consumed++;
+        if (len == 0) break;
+        if ((len & 0xC0) == 0xC0) {
+            if (pos + 1 >= n) return "Truncated";
+            const size_t pointer = ((size_t)(len & 0x3F) << 8) | buf[pos + 1];
+            if (pointer >= n) return "InvalidCompression";
+            for (size_t v : visited)
+                if (v == pointer) return "CompressionLoop";
+            visited.push_back(pointer);
+            if (++depth > 16) return "CompressionLoop";
+            if (!jumped) out.consumed++;
+            pos = pointer;
+            jumped = true;
+            continue;
+        }
+        if (len & 0xC0) return "InvalidCompression";
+        pos++;
+        if (pos + len > n) return "Truncated";
+        if (!utf8(buf + pos, len)) return "InvalidUtf8";
+        if (!first) out.name += '.';
+        first = false;
+        out.name.append(reinterpret_cast<const char*>(buf + pos), len);
+        if (!jumped) out.consumed += len;
+        pos += len;
+    }
+    return out;
+}
 
 /* ---- addresses and headers -------------------------------------------- */
 
@@ -918,6 +993,72 @@ class Engine {  // one nexg context on one gfx950 device, one stream
         check_hip(hipMemcpyAsync(len.data(), d_len, n * 4, hipMemcpyDeviceToHost, stream_), "D2H");
         check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
         for (uint64_t i = 0; i < n; i++) out[i] = Decap{tun[i], (uint32_t)(off[i] - hb.offs[i]), len[i]};
+        return out;
+    }
+
+    // The DNS message pass over a device-resident batch already parsed with
+    // NEXG_OUT_RECORD (DnsPacket::try_from_buf dns.rs:1166-1259 on
+    // Frame.payload): `out` holds frames.count summaries, tile_first
+    // nexg_dns_tile_first_bytes(frames.count) bytes; its last element is the
+    // number of entries. any_udp: every UDP frame with a non-empty payload is
+    // tried (dns_dump.rs:98-100), else those from or to `port`.
+    void dns(const nexg_frames& frames, const nexg_record* records, nexg_dns* out, uint64_t* tile_first,
+             uint16_t port = 53, bool any_udp = false) {
+        DeviceScope ds(device_);
+        const nexg_dns_option o{any_udp ? NEXG_DNS_ANY_UDP : 0u, port, 0};
+        check(nexg_dns_batch(ctx_, &frames, records, &o, out, tile_first, stream_), "nexg_dns_batch");
+    }
+
+    // One nexg_dns_entry per query / resource record: the k-th entry of frame
+    // i at tile_first[i >> 8] + dns[i].first + k; nothing at or past entries_cap
+    void dns_entries(const nexg_frames& frames, const nexg_dns* dns, const uint64_t* tile_first,
+                     nexg_dns_entry* entries, uint64_t entries_cap) {
+        DeviceScope ds(device_);
+        check(nexg_dns_entries(ctx_, &frames, dns, tile_first, entries, entries_cap, stream_), "nexg_dns_entries");
+    }
+
+    // The DNS message of every host frame: parse (NEXG_OUT_RECORD) + dns +
+    // dns_entries on the device, sized exactly (one stream synchronisation
+    // for the total); frame i's rows are entries[row[i], row[i + 1])
+    struct DnsBatch {
+        std::vector<nexg_dns> dns;
+        std::vector<uint64_t> row;  // frames + 1
+        std::vector<nexg_dns_entry> entries;
+    };
+    DnsBatch dns_bufs(const std::vector<std::vector<uint8_t>>& frames, ParseOption option = {}, uint16_t port = 53,
+                      bool any_udp = false) {
+        DeviceScope ds(device_);
+        const uint64_t n = frames.size();
+        DnsBatch out;
+        out.row.assign(n + 1, 0);
+        if (n == 0) return out;
+        HostBatch hb(*this, frames);
+        void* d_recs = scratch(3, n * 64);
+        nexg_dns* d_dns = static_cast<nexg_dns*>(scratch(18, n * sizeof(nexg_dns)));
+        const uint64_t tiles = (n + 255) / 256;
+        uint64_t* d_tf = static_cast<uint64_t*>(scratch(19, nexg_dns_tile_first_bytes(n)));
+        parse(hb.fb, option, ParseMode::Lenient, NEXG_OUT_RECORD, d_recs);
+        dns(hb.fb, static_cast<const nexg_record*>(d_recs), d_dns, d_tf, port, any_udp);
+        std::vector<uint64_t> tf(tiles + 1);
+        out.dns.resize(n);
+        check_hip(hipMemcpyAsync(tf.data(), d_tf, (tiles + 1) * 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipMemcpyAsync(out.dns.data(), d_dns, n * sizeof(nexg_dns), hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        const uint64_t total = tf[tiles];
+        out.entries.resize(total);
+        if (total) {
+            nexg_dns_entry* d_ent = static_cast<nexg_dns_entry*>(scratch(20, total * sizeof(nexg_dns_entry)));
+            dns_entries(hb.fb, d_dns, d_tf, d_ent, total);
+            check_hip(hipMemcpyAsync(out.entries.data(), d_ent, total * sizeof(nexg_dns_entry), hipMemcpyDeviceToHost,
+                                     stream_),
+                      "D2H");
+            check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        }
+        for (uint64_t i = 0; i < n; i++) {
+            const nexg_dns& s = out.dns[i];
+            out.row[i] = tf[i >> 8] + s.first;
+            out.row[i + 1] = out.row[i] + s.n_q + s.n_an + s.n_ns + s.n_ar;
+        }
         return out;
     }
 

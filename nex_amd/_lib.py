@@ -51,6 +51,8 @@ def load():
         "nexg_decode_options": (I, [P, ctypes.POINTER(abi.Frames), P, P, P]),
         "nexg_decap_batch": (I, [P, ctypes.POINTER(abi.Frames), P, ctypes.POINTER(abi.DecapOption), P, P, P, P]),
         "nexg_decap_select": (I, [P, P, P, P, U64, U32, P, P, P, P, P, U64, P]),
+        "nexg_dns_batch": (I, [P, ctypes.POINTER(abi.Frames), P, ctypes.POINTER(abi.DnsOption), P, P, P]),
+        "nexg_dns_entries": (I, [P, ctypes.POINTER(abi.Frames), P, P, P, U64, P]),
         "nexg_build_udp4_batch": (I, [P, ctypes.POINTER(abi.Udp4Build), P, U32, P]),
         "nexg_build_udp4_tuples": (I, [P, ctypes.POINTER(abi.Udp4Build), P, P, U32, P]),
         "nexg_build_udp6_batch": (I, [P, ctypes.POINTER(abi.Udp6Build), P, U32, P]),

@@ -413,15 +413,41 @@ def decap_select_workspace(count):
     return 4 * ((tiles + 255) // 256 * 256) + 16
 
 
+# DNS messages (nexg_dns_batch / nexg_dns_entries)
+DNS_ANY_UDP = 0x1
+DNS_PORT = 53  # what nexg_dns_option.port = 0 means
+DNS_CANDIDATE = 0x1    # nexg_dns.flags8
+DNS_SECTION_SHORT = 0x2
+DNS_DATA_CUT = 0x1     # nexg_dns_entry.flags8
+DNS_QUERY, DNS_ANSWER, DNS_AUTHORITY, DNS_ADDITIONAL = 0, 1, 2, 3  # nexg_dns_entry.section
+DNS_DTYPE = np.dtype([("status", "u1"), ("flags8", "u1"), ("msg_off", "<u2"), ("msg_len", "<u2"), ("id", "<u2"),
+                      ("flags", "<u2"), ("qd", "<u2"), ("an", "<u2"), ("ns", "<u2"), ("ar", "<u2"), ("n_q", "<u2"),
+                      ("n_an", "<u2"), ("n_ns", "<u2"), ("n_ar", "<u2"), ("rest_off", "<u2"), ("first", "<u4")])
+assert DNS_DTYPE.itemsize == 32
+DNS_ENTRY_DTYPE = np.dtype([("section", "u1"), ("flags8", "u1"), ("off", "<u2"), ("type", "<u2"),
+                            ("dns_class", "<u2"), ("ttl", "<u4"), ("name", "<u2"), ("data_len", "<u2")])
+assert DNS_ENTRY_DTYPE.itemsize == 16
+
+
+class DnsOption(ctypes.Structure):
+    """struct nexg_dns_option"""
+    _fields_ = [("flags", ctypes.c_uint32), ("port", ctypes.c_uint16), ("reserved", ctypes.c_uint16)]
+
+
+def dns_tile_first_bytes(count):
+    """nexg_dns_tile_first_bytes: bytes of nexg_dns_batch's tile_first."""
+    return 8 * ((int(count) + 255) // 256 + 1)
+
+
 #: static inline helpers of include/nexg.h (header-only, not exported)
 HEADER_INLINE = ("nexg_sparse_decode", "nexg_grouped_code", "nexg_grouped_exc_slot", "nexg_offsets32_bases",
-                 "nexg_offsets32_bytes", "nexg_decap_select_workspace")
+                 "nexg_offsets32_bytes", "nexg_decap_select_workspace", "nexg_dns_tile_first_bytes")
 
 #: every symbol include/nexg.h declares (tests check the .so exports them)
 EXPORTED_SYMBOLS = (
     "nexg_abi_version", "nexg_strerror", "nexg_ctx_create", "nexg_ctx_destroy",
     "nexg_ctx_last_error", "nexg_ctx_cu_count", "nexg_parse_batch", "nexg_checksum_batch", "nexg_decode_options", "nexg_probe_stream",
-    "nexg_decap_batch", "nexg_decap_select",
+    "nexg_decap_batch", "nexg_decap_select", "nexg_dns_batch", "nexg_dns_entries",
     "nexg_probe_span_clock", "nexg_probe_latency",
     "nexg_sparse_expand", "nexg_grouped_expand", "nexg_recompute_checksums_batch",
     "nexg_rx_config_default", "nexg_rx_open", "nexg_rx_next_batch", "nexg_rx_stats", "nexg_rx_close",

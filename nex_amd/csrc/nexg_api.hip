@@ -302,6 +302,50 @@ int nexg_decap_select(nexg_ctx* ctx, const nexg_tunnel* tunnels, const uint64_t*
                       NEXG_ELAUNCH);
 }
 
+int nexg_dns_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records,
+                   const nexg_dns_option* option, nexg_dns* out, uint64_t* tile_first, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    uint32_t flags = 0u, port = 53u;
+    if (option) {
+        if (option->reserved != 0) return fail(ctx, NEXG_EINVAL, "dns option: reserved must be 0%s", nullptr);
+        if ((option->flags & ~NEXG_DNS_ANY_UDP) != 0)
+            return fail(ctx, NEXG_EINVAL, "dns option: unknown flag bits%s", nullptr);
+        flags = option->flags;
+        if (option->port) port = option->port;
+    }
+    if (frames->count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "dns: more than 2^32 - 1 frames%s", nullptr);
+    if (frames->count && (!records || !out || !tile_first))
+        return fail(ctx, NEXG_EINVAL, "NULL records or output%s", nullptr);
+    if (((reinterpret_cast<uint64_t>(records) | reinterpret_cast<uint64_t>(out)) & 15u) != 0 ||
+        (reinterpret_cast<uint64_t>(tile_first) & 7u) != 0)
+        return fail(ctx, NEXG_EINVAL, "misaligned records or output%s", nullptr);
+    if (!tile_first) return NEXG_OK;  // an empty batch with nowhere to put its total
+    const nexg::ParseArgs a = to_args(frames);
+    DeviceGuard g(ctx);
+    return hip_status(ctx, nexg::launch_dns(a, records, flags & NEXG_DNS_ANY_UDP, port, out, tile_first,
+                                            static_cast<hipStream_t>(stream)),
+                      NEXG_ELAUNCH);
+}
+
+int nexg_dns_entries(nexg_ctx* ctx, const nexg_frames* frames, const nexg_dns* dns, const uint64_t* tile_first,
+                     nexg_dns_entry* entries, uint64_t entries_cap, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    if (frames->count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "dns: more than 2^32 - 1 frames%s", nullptr);
+    if (frames->count && (!dns || !tile_first)) return fail(ctx, NEXG_EINVAL, "NULL summaries or tile_first%s", nullptr);
+    if (entries_cap && !entries) return fail(ctx, NEXG_EINVAL, "NULL entries with a nonzero capacity%s", nullptr);
+    if (((reinterpret_cast<uint64_t>(dns) | reinterpret_cast<uint64_t>(entries)) & 15u) != 0 ||
+        (reinterpret_cast<uint64_t>(tile_first) & 7u) != 0)
+        return fail(ctx, NEXG_EINVAL, "misaligned summaries, tile_first or entries%s", nullptr);
+    if (!entries) return NEXG_OK;  // capacity 0: nothing to store
+    const nexg::ParseArgs a = to_args(frames);
+    DeviceGuard g(ctx);
+    return hip_status(ctx, nexg::launch_dns_entries(a, dns, tile_first, entries, entries_cap,
+                                                    static_cast<hipStream_t>(stream)),
+                      NEXG_ELAUNCH);
+}
+
 int nexg_probe_stream(nexg_ctx* ctx, const void* data, uint64_t bytes, uint32_t out_per_64,
                       void* out, void* stream) {
     if (!ctx) return NEXG_EINVAL;

@@ -110,6 +110,13 @@ hipError_t launch_decap_select(const nexg_tunnel* tunnels, const uint64_t* inner
                                uint64_t count, uint32_t inner_mask, uint32_t* out_index, uint64_t* out_off,
                                uint32_t* out_len, uint64_t* out_count, uint32_t* tile_count, hipStream_t s);
 
+// nexg_dns_batch / nexg_dns_entries (nexg_dns.hip). tile_first: one u64 per
+// 256-frame tile + 1, left holding the tiles' exclusive scan and the total.
+hipError_t launch_dns(const ParseArgs& a, const nexg_record* recs, uint32_t any_udp, uint32_t port, nexg_dns* out,
+                      uint64_t* tile_first, hipStream_t s);
+hipError_t launch_dns_entries(const ParseArgs& a, const nexg_dns* dns, const uint64_t* tile_first,
+                              nexg_dns_entry* entries, uint64_t cap, hipStream_t s);
+
 hipError_t launch_probe_stream(const uint8_t* data, uint64_t tiles, uint32_t mode, void* out, hipStream_t s);
 hipError_t launch_probe_latency(uint32_t* buf, uint32_t lines, uint32_t start, uint32_t steps, uint32_t loaded_wgs,
                                 uint32_t rounds, uint64_t* out, hipStream_t s);

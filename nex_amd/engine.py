@@ -340,6 +340,45 @@ class Engine:
         k = int(cnt.item())  # waits for the kernels
         return idx[:k], FrameBatch(data=inner.data, count=k, offsets=off[:k], lengths=ln[:k], hints=inner.hints)
 
+    def dns(self, batch: FrameBatch, records, port: int = abi.DNS_PORT, any_udp: bool = False, entries_cap=None,
+            stream=None):
+        """Walk every DNS message of `batch` in place (nexg_dns_batch +
+        nexg_dns_entries; DnsPacket::try_from_buf dns.rs:1166-1259 on
+        Frame.payload). `records` is the uint8 device tensor a NEXG_OUT_RECORD
+        parse of `batch` returned. A frame is tried when it is UDP with a
+        non-empty payload from or to `port` (any_udp: every such UDP frame,
+        as dns_dump.rs:98-100 does).
+
+        Returns (dns, tile_first, entries, total): uint8 device tensors
+        holding nexg_dns[count] (abi.DNS_DTYPE) and nexg_dns_entry rows
+        (abi.DNS_ENTRY_DTYPE), tile_first an int64 device tensor of
+        ceil(count / 256) + 1 prefix sums. The k-th entry of frame i is row
+        tile_first[i >> 8] + dns[i].first + k (nex_amd.dns.frame_entries).
+
+        entries_cap=None reads the total back (one synchronisation of the
+        stream), allocates exactly that many rows and fills them; total is
+        then an int. With a capacity given both calls are enqueued without a
+        synchronisation, rows at or past the capacity are not written, and
+        total is the one-element device tensor tile_first[-1:]."""
+        torch = _torch()
+        n = batch.count
+        dev = self.torch_device
+        out = torch.empty(max(n, 1) * 32, dtype=torch.uint8, device=dev)
+        tile_first = torch.empty(abi.dns_tile_first_bytes(n) // 8, dtype=torch.int64, device=dev)
+        fr = batch.to_c()
+        opt = abi.DnsOption(abi.DNS_ANY_UDP if any_udp else 0, port, 0)
+        s = self._stream(stream)
+        self._check(self.lib.nexg_dns_batch(self.ctx, ctypes.byref(fr), _ptr(records), ctypes.byref(opt), _ptr(out),
+                                            _ptr(tile_first), s))
+        if entries_cap is None:
+            total = cap = int(tile_first[-1].item())  # waits for the kernels
+        else:
+            total, cap = tile_first[-1:], int(entries_cap)
+        entries = torch.empty(max(cap, 1) * 16, dtype=torch.uint8, device=dev)
+        self._check(self.lib.nexg_dns_entries(self.ctx, ctypes.byref(fr), _ptr(out), _ptr(tile_first), _ptr(entries),
+                                              cap, s))
+        return out[: n * 32], tile_first, entries[: cap * 16], total
+
     def probe_stream(self, data, write8, out=None, stream=None):
         """Calibration stream over a uint8 device tensor (nexg_probe_stream):
         the parse kernels' load shape, read-only or with the 8-B-per-64-B
