@@ -729,6 +729,152 @@ int nexg_dns_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* 
 int nexg_dns_entries(nexg_ctx* ctx, const nexg_frames* frames, const nexg_dns* dns,
                      const uint64_t* tile_first, nexg_dns_entry* entries, uint64_t entries_cap, void* stream);
 
+/* ---- frame selection by rule, and gather (extension) --------------------------
+ * The reference has no filter (examples/dump.rs prints every frame); like
+ * NEXG_PARSE_VLAN this is an extension, and the text below is its whole
+ * specification (nex_amd/select.py match_host / gather_host restate it on the
+ * host). nexg_select_batch picks frames of a batch already parsed with
+ * NEXG_OUT_RECORD by tests on the record's fields and writes a frame table
+ * over the same bytes; nexg_gather_plan / nexg_gather_frames copy the selected
+ * frames into one dense buffer, nexg_gather_rows compacts any per-frame rows.
+ *
+ * A filter is 1..16 rules. A rule is a conjunction of tests; a frame matches
+ * the filter when some rule matches; NEXG_FILTER_INVERT flips the verdict.
+ * The flags test ((record.flags & flags_mask) == flags_value; 0 / 0 is always
+ * true; it covers the layer bits, the NEXG_C_* verdicts, NEXG_L_VLAN and the
+ * status in bits 24..26) is always evaluated, the others when their bit is set
+ * in `tests`:
+ *   NEXG_RULE_PROTO      NEXG_L_IPV4 or NEXG_L_IPV6, and record.ip_proto == ip_proto
+ *   NEXG_RULE_SRC_PORT   NEXG_L_TCP or NEXG_L_UDP, and src_port in [sport_lo, sport_hi]
+ *   NEXG_RULE_DST_PORT   NEXG_L_TCP or NEXG_L_UDP, and dst_port in [dport_lo, dport_hi]
+ *   NEXG_RULE_ANY_PORT   NEXG_L_TCP or NEXG_L_UDP, and either port in [sport_lo, sport_hi]
+ *                        (dport_lo / dport_hi must be 0; not with SRC_PORT / DST_PORT)
+ *   NEXG_RULE_SRC_ADDR   the source address matches the first src_bits bits of src
+ *   NEXG_RULE_DST_ADDR   the destination address matches the first dst_bits bits of dst
+ *   NEXG_RULE_ANY_ADDR   either address matches the first src_bits bits of src
+ *                        (dst_bits must be 0; not with SRC_ADDR / DST_ADDR)
+ *   NEXG_RULE_TCP_FLAGS  NEXG_L_TCP and (record.l4_type & tcp_mask) == tcp_value
+ *   NEXG_RULE_LENGTH     len_lo <= len(i) <= len_hi, len(i) as the frame table gives it
+ * Address tests, family 4: the frame must have NEXG_L_IPV4; the addresses are
+ * record.ip_src / ip_dst (an ARP frame never matches: pick those with the flags
+ * test). Family 6: the frame must have NEXG_L_IPV6, a valid extent and
+ * l3_off + 40 <= len(i); the addresses are frame bytes [l3_off + 8, l3_off + 24)
+ * and [l3_off + 24, l3_off + 40) (the record does not carry them). The port
+ * tests need a TCP or UDP layer because the record reuses the port fields for
+ * ARP. A record whose status is not 0 carries an error payload in its address,
+ * port and type fields: for such a frame every test but the flags test and the
+ * length test is false.
+ *
+ * Records are caller memory: nothing outside a frame's own extent is read (the
+ * 16-B block rule of the frame batch layout applies), and a record whose l3_off
+ * points past its frame simply fails the family-6 address tests. A filter
+ * without a family-6 rule reads no frame byte.
+ *
+ * NEXG_EINVAL (nexg_filter_check says which): n_rules 0 or above 16, unknown
+ * `tests` or `flags` bits, reserved != 0, an address test with a family other
+ * than 4 or 6, prefix bits above the family's width, lo > hi in a range under
+ * test, the exclusive combinations above. */
+#define NEXG_RULE_PROTO 0x1u
+#define NEXG_RULE_SRC_PORT 0x2u
+#define NEXG_RULE_DST_PORT 0x4u
+#define NEXG_RULE_ANY_PORT 0x8u
+#define NEXG_RULE_SRC_ADDR 0x10u
+#define NEXG_RULE_DST_ADDR 0x20u
+#define NEXG_RULE_ANY_ADDR 0x40u
+#define NEXG_RULE_TCP_FLAGS 0x80u
+#define NEXG_RULE_LENGTH 0x100u
+#define NEXG_RULE_ALL 0x1FFu
+#define NEXG_FILTER_INVERT 0x1u
+#define NEXG_FILTER_MAX_RULES 16
+#define NEXG_RULE_NONE 0xFFu /* out_rule under NEXG_FILTER_INVERT */
+typedef struct nexg_rule {      /* 64 bytes */
+    uint32_t flags_mask;        /* (record.flags & flags_mask) == flags_value; 0/0 always true */
+    uint32_t flags_value;
+    uint32_t tests;             /* NEXG_RULE_*; unknown bits -> NEXG_EINVAL */
+    uint8_t ip_proto;           /* NEXG_RULE_PROTO */
+    uint8_t tcp_mask, tcp_value; /* NEXG_RULE_TCP_FLAGS */
+    uint8_t family;             /* address tests: 4 or 6 */
+    uint8_t src_bits, dst_bits; /* prefix lengths: 0..32 / 0..128 */
+    uint16_t reserved;          /* must be 0 */
+    uint16_t sport_lo, sport_hi, dport_lo, dport_hi; /* inclusive ranges */
+    uint16_t len_lo, len_hi;    /* NEXG_RULE_LENGTH */
+    uint8_t src[16], dst[16];   /* network order; family 4 uses the first 4 bytes */
+} nexg_rule;
+typedef struct nexg_filter { /* host memory; read during the call, not after it */
+    uint32_t n_rules;
+    uint32_t flags; /* NEXG_FILTER_* */
+    nexg_rule rules[NEXG_FILTER_MAX_RULES];
+} nexg_filter;
+
+/* NEXG_OK when nexg_select_batch would accept the filter, else NEXG_EINVAL.
+ * Host only: no context, no device. */
+int nexg_filter_check(const nexg_filter* filter);
+
+/* Order-preserving selection. records[i] = frame i's record (16-B aligned;
+ * e.g. the inner records with an inner table from nexg_decap_batch). For the
+ * k-th selected frame in index order out_index[k] = i, out_off[k] = off(i),
+ * out_len[k] = len(i) exactly as the input table defines them for any layout
+ * (a length above 2^32 - 1 is stored as 2^32 - 1), out_rule[k] (optional, may
+ * be NULL) = the lowest matching rule index, NEXG_RULE_NONE under
+ * NEXG_FILTER_INVERT; *out_count (device memory, 8-B aligned) = the number
+ * selected. {frames->data, frames->data_bytes, out_off, out_len, *out_count}
+ * is then a valid offsets + lengths table over the same bytes, monotone
+ * whenever the input was packed, fixed-stride or monotone. The output arrays
+ * have capacity `count` (out_off 8-B, out_index / out_len 4-B aligned); count
+ * must not exceed 2^32 - 1. workspace: caller-owned device memory (4-B
+ * aligned) of at least nexg_select_workspace(count) bytes, one u32 per
+ * 256-frame tile. Positions come from ballots, ranks and scans only (no
+ * atomics): a run repeats bit for bit. count == 0 writes *out_count = 0 and
+ * launches nothing else. The scatter bounds every store by `count`, whatever
+ * the workspace holds. NEXG_EINVAL: an invalid filter or frame table, a NULL
+ * pointer, a misaligned pointer, a short workspace. Three kernels on `stream`. */
+int nexg_select_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records,
+                      const nexg_filter* filter, uint32_t* out_index, uint64_t* out_off, uint32_t* out_len,
+                      uint8_t* out_rule, uint64_t* out_count, void* workspace, uint64_t workspace_bytes,
+                      void* stream);
+static inline uint64_t nexg_select_workspace(uint64_t count) {
+    const uint64_t tiles = (count + 255u) / 256u;
+    return 4u * ((tiles + 255u) / 256u * 256u) + 16u;
+}
+
+/* Gather, in two calls (as nexg_dns_batch / nexg_dns_entries: the host reads
+ * one total, allocates, then fills). `sel` is any frame table, usually the one
+ * nexg_select_batch wrote. copied(k) = len(k), or 0 when the frame's extent
+ * leaves [0, data_bytes) or its length exceeds 65535.
+ *
+ * nexg_gather_plan: out_offsets[k] (count + 1 entries, 8-B aligned) = the sum
+ * over j < k of copied(j) rounded up to `align` (1, 4, 8 or 16);
+ * out_offsets[count] = the total; out_len[k] (optional, may be NULL) =
+ * copied(k). workspace: device memory (8-B aligned) of at least
+ * nexg_gather_plan_workspace(count) bytes, one u64 per 256-frame tile. count
+ * must not exceed 2^32 - 1. count == 0 writes out_offsets[0] = 0. Scans only,
+ * no atomics. Three kernels on `stream`.
+ *
+ * nexg_gather_frames: bytes [out_offsets[k], out_offsets[k] + copied(k)) of
+ * out_data (16-B aligned) become frame k's bytes, the pad bytes up to
+ * out_offsets[k + 1] zero. No byte at or past out_cap is stored, whatever
+ * out_offsets holds (it is caller memory), and bytes from the total up to
+ * out_cap are left alone. Source reads follow the 16-B block rule and never
+ * leave a frame's blocks. With align 1, {out_data, total, out_offsets} is a
+ * packed batch; with a larger align, {out_data, total, out_offsets, out_len}
+ * an offsets + lengths batch (monotone).
+ *
+ * nexg_gather_rows: out row k = rows[index[k]] when index[k] < rows_count,
+ * zeros otherwise, for k < n (n <= 2^32 - 1). row_bytes is 4, 8, 16, 32 or
+ * 64; rows and out are aligned to min(row_bytes, 16), index to 4. It compacts
+ * records, nexg_tunnel, nexg_dns, descriptors and flags words by the index
+ * nexg_select_batch returned. n == 0 launches nothing. */
+int nexg_gather_plan(nexg_ctx* ctx, const nexg_frames* sel, uint32_t align, uint64_t* out_offsets,
+                     uint32_t* out_len, void* workspace, uint64_t workspace_bytes, void* stream);
+static inline uint64_t nexg_gather_plan_workspace(uint64_t count) {
+    const uint64_t tiles = (count + 255u) / 256u;
+    return 8u * ((tiles + 255u) / 256u * 256u) + 16u;
+}
+int nexg_gather_frames(nexg_ctx* ctx, const nexg_frames* sel, const uint64_t* out_offsets, uint8_t* out_data,
+                       uint64_t out_cap, void* stream);
+int nexg_gather_rows(nexg_ctx* ctx, const void* rows, uint32_t row_bytes, uint64_t rows_count,
+                     const uint32_t* index, uint64_t n, void* out, void* stream);
+
 /* ---- calibration (not a reference entry point) ---------------------------
  * The HBM stream ceilings the parse kernels are measured against, on the
  * caller's own buffer and box: `bytes` (a multiple of 16384) read with the

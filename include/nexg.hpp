@@ -23,6 +23,10 @@
  *   Engine::dns / dns_entries / dns_bufs   DnsPacket::try_from_buf
  *                           (dns.rs:1166-1259) on every UDP payload of a batch;
  *                           decode_dns_name   dns.rs:1303-1390 (on the host)
+ *   Filter, Engine::select / gather_plan / gather / gather_rows / select_bufs
+ *                           no reference counterpart (an extension): frames
+ *                           picked by rules over the parsed fields, and the
+ *                           gather of their bytes and rows (include/nexg.h)
  * The device does the parse and the checksums (nexg_parse_batch,
  * NEXG_OUT_RECORD) and the option lists (nexg_decode_options); this header
  * only reads header fields out of the frame bytes at the offsets the device
@@ -884,6 +888,115 @@ inline std::vector<uint8_t> message_bytes(const Icmpv6Packet& p) {
 }  // namespace ndp
 }  // namespace icmpv6
 
+/* ---- frame selection (extension: the reference has no filter) ------------- */
+
+// Builder of a nexg_filter (include/nexg.h): any / flags / udp / tcp / status /
+// bad_checksum_* append a rule; proto / *_port / length / *_net4 / *_net6 add a
+// further test to the last rule. get() throws nexg::Error where
+// nexg_select_batch would return NEXG_EINVAL.
+//   Filter().tcp(0x12, 0x02).dst_net4({10, 0, 0, 0}, 8)      TCP SYNs to 10/8
+//           .udp().any_port(53)                              or UDP port 53
+//           .bad_checksum_l4()                               or a failed L4 checksum
+class Filter {
+   public:
+    nexg_filter f{};
+
+    Filter& rule(const nexg_rule& r) {
+        if (f.n_rules >= NEXG_FILTER_MAX_RULES) throw Error("Filter: more than 16 rules");
+        f.rules[f.n_rules++] = r;
+        return *this;
+    }
+    Filter& any() { return rule(nexg_rule{}); }
+    Filter& flags(uint32_t mask, uint32_t value) {
+        nexg_rule r{};
+        r.flags_mask = mask;
+        r.flags_value = value;
+        return rule(r);
+    }
+    Filter& udp() { return flags(NEXG_L_UDP, NEXG_L_UDP); }
+    // TCP frames; tcp_mask != 0 adds (flags & tcp_mask) == tcp_value on the TCP flags byte
+    Filter& tcp(uint8_t tcp_mask = 0, uint8_t tcp_value = 0) {
+        flags(NEXG_L_TCP, NEXG_L_TCP);
+        if (tcp_mask) {
+            last().tests |= NEXG_RULE_TCP_FLAGS;
+            last().tcp_mask = tcp_mask;
+            last().tcp_value = tcp_value;
+        }
+        return *this;
+    }
+    Filter& status(uint32_t code) { return flags(7u << NEXG_STATUS_SHIFT, code << NEXG_STATUS_SHIFT); }
+    Filter& bad_checksum_l4() { return flags(NEXG_C_L4_CHECKED | NEXG_C_L4_OK, NEXG_C_L4_CHECKED); }
+    Filter& bad_checksum_ip() { return flags(NEXG_C_IP_CHECKED | NEXG_C_IP_OK, NEXG_C_IP_CHECKED); }
+    Filter& invert(bool on = true) {
+        f.flags = on ? NEXG_FILTER_INVERT : 0u;
+        return *this;
+    }
+    // further tests on the last rule (a new match-all rule when there is none)
+    Filter& proto(uint8_t p) {
+        last().tests |= NEXG_RULE_PROTO;
+        last().ip_proto = p;
+        return *this;
+    }
+    Filter& any_port(uint16_t lo, uint16_t hi) {
+        last().tests |= NEXG_RULE_ANY_PORT;
+        last().sport_lo = lo;
+        last().sport_hi = hi;
+        return *this;
+    }
+    Filter& any_port(uint16_t p) { return any_port(p, p); }
+    Filter& src_port(uint16_t lo, uint16_t hi) {
+        last().tests |= NEXG_RULE_SRC_PORT;
+        last().sport_lo = lo;
+        last().sport_hi = hi;
+        return *this;
+    }
+    Filter& dst_port(uint16_t lo, uint16_t hi) {
+        last().tests |= NEXG_RULE_DST_PORT;
+        last().dport_lo = lo;
+        last().dport_hi = hi;
+        return *this;
+    }
+    Filter& length(uint16_t lo, uint16_t hi) {
+        last().tests |= NEXG_RULE_LENGTH;
+        last().len_lo = lo;
+        last().len_hi = hi;
+        return *this;
+    }
+    Filter& src_net4(const std::array<uint8_t, 4>& a, uint8_t bits) { return addr(NEXG_RULE_SRC_ADDR, 4, a.data(), 4, bits); }
+    Filter& dst_net4(const std::array<uint8_t, 4>& a, uint8_t bits) { return addr(NEXG_RULE_DST_ADDR, 4, a.data(), 4, bits); }
+    Filter& any_net4(const std::array<uint8_t, 4>& a, uint8_t bits) { return addr(NEXG_RULE_ANY_ADDR, 4, a.data(), 4, bits); }
+    Filter& src_net6(const std::array<uint8_t, 16>& a, uint8_t bits) { return addr(NEXG_RULE_SRC_ADDR, 6, a.data(), 16, bits); }
+    Filter& dst_net6(const std::array<uint8_t, 16>& a, uint8_t bits) { return addr(NEXG_RULE_DST_ADDR, 6, a.data(), 16, bits); }
+    Filter& any_net6(const std::array<uint8_t, 16>& a, uint8_t bits) { return addr(NEXG_RULE_ANY_ADDR, 6, a.data(), 16, bits); }
+
+    // the filter, checked as nexg_select_batch checks it
+    const nexg_filter& get() const {
+        if (nexg_filter_check(&f) != NEXG_OK) throw Error("Filter: not a valid nexg_filter (include/nexg.h)");
+        return f;
+    }
+
+   private:
+    nexg_rule& last() {
+        if (f.n_rules == 0) any();
+        return f.rules[f.n_rules - 1];
+    }
+    Filter& addr(uint32_t test, uint8_t family, const uint8_t* a, size_t n, uint8_t bits) {
+        nexg_rule& r = last();
+        if ((r.tests & (NEXG_RULE_SRC_ADDR | NEXG_RULE_DST_ADDR | NEXG_RULE_ANY_ADDR)) && r.family != family)
+            throw Error("Filter: address tests of two families in one rule");
+        r.tests |= test;
+        r.family = family;
+        if (test == NEXG_RULE_DST_ADDR) {
+            memcpy(r.dst, a, n);
+            r.dst_bits = bits;
+        } else {
+            memcpy(r.src, a, n);
+            r.src_bits = bits;
+        }
+        return *this;
+    }
+};
+
 /* ---- the engine --------------------------------------------------------- */
 
 // The calling thread's current device switched for a scope and restored after
@@ -1059,6 +1172,113 @@ class Engine {  // one nexg context on one gfx950 device, one stream
             out.row[i] = tf[i >> 8] + s.first;
             out.row[i + 1] = out.row[i] + s.n_q + s.n_an + s.n_ns + s.n_ar;
         }
+        return out;
+    }
+
+    // Order-preserving selection of the frames of a device-resident batch
+    // already parsed with NEXG_OUT_RECORD that match `filter` (an extension,
+    // include/nexg.h nexg_select_batch): device arrays of capacity
+    // frames.count (out_rule may be null); returns the number selected (one
+    // stream synchronisation). {frames.data, frames.data_bytes, out_off,
+    // out_len, returned count} is the selected batch: parse, decap and dns
+    // take it as it stands, with gather_rows(records, 64, ...) for its records.
+    uint64_t select(const nexg_frames& frames, const nexg_record* records, const Filter& filter, uint32_t* out_index,
+                    uint64_t* out_off, uint32_t* out_len, uint8_t* out_rule = nullptr) {
+        DeviceScope ds(device_);
+        const uint64_t wsb = nexg_select_workspace(frames.count);
+        void* ws = scratch(21, wsb);
+        uint64_t* d_count = static_cast<uint64_t*>(scratch(22, 8));
+        check(nexg_select_batch(ctx_, &frames, records, &filter.get(), out_index, out_off, out_len, out_rule, d_count,
+                                ws, wsb, stream_),
+              "nexg_select_batch");
+        uint64_t k = 0;
+        check_hip(hipMemcpyAsync(&k, d_count, 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        return k;
+    }
+
+    // Where gather puts each frame of `sel` (nexg_gather_plan): out_offsets
+    // holds sel.count + 1 entries, out_len (may be null) sel.count; returns
+    // the total bytes (one stream synchronisation) to allocate for gather
+    uint64_t gather_plan(const nexg_frames& sel, uint32_t align, uint64_t* out_offsets, uint32_t* out_len) {
+        DeviceScope ds(device_);
+        const uint64_t wsb = nexg_gather_plan_workspace(sel.count);
+        void* ws = scratch(23, wsb);
+        check(nexg_gather_plan(ctx_, &sel, align, out_offsets, out_len, ws, wsb, stream_), "nexg_gather_plan");
+        uint64_t total = 0;
+        check_hip(hipMemcpyAsync(&total, out_offsets + sel.count, 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        return total;
+    }
+
+    // The frames of `sel` copied to out_data at the planned offsets, pads
+    // zero, nothing at or past out_cap (nexg_gather_frames)
+    void gather(const nexg_frames& sel, const uint64_t* out_offsets, uint8_t* out_data, uint64_t out_cap) {
+        DeviceScope ds(device_);
+        check(nexg_gather_frames(ctx_, &sel, out_offsets, out_data, out_cap, stream_), "nexg_gather_frames");
+    }
+
+    // out row k = rows[index[k]] (zeros when index[k] >= rows_count): records,
+    // tunnels, DNS summaries, descriptors or flags words of the selected frames
+    void gather_rows(const void* rows, uint32_t row_bytes, uint64_t rows_count, const uint32_t* index, uint64_t n,
+                     void* out) {
+        DeviceScope ds(device_);
+        check(nexg_gather_rows(ctx_, rows, row_bytes, rows_count, index, n, out, stream_), "nexg_gather_rows");
+    }
+
+    // parse (NEXG_OUT_RECORD) + select + gather of host frames: the selected
+    // frames' numbers, first matching rules, records, and their bytes as one
+    // dense buffer with count + 1 offsets (each start rounded up to `align`)
+    struct Selected {
+        std::vector<uint32_t> index;
+        std::vector<uint8_t> rule;
+        std::vector<nexg_record> records;
+        std::vector<uint64_t> offsets;  // index.size() + 1
+        std::vector<uint32_t> lengths;
+        std::vector<uint8_t> data;
+    };
+    Selected select_bufs(const std::vector<std::vector<uint8_t>>& frames, const Filter& filter, ParseOption option = {},
+                         ParseMode mode = ParseMode::Lenient, uint32_t align = 1) {
+        DeviceScope ds(device_);
+        const uint64_t n = frames.size();
+        Selected out;
+        out.offsets.assign(1, 0);
+        if (n == 0) return out;
+        HostBatch hb(*this, frames);
+        nexg_record* d_recs = static_cast<nexg_record*>(scratch(3, n * 64));
+        uint32_t* d_idx = static_cast<uint32_t*>(scratch(24, n * 4));
+        uint64_t* d_off = static_cast<uint64_t*>(scratch(25, n * 8));
+        uint32_t* d_len = static_cast<uint32_t*>(scratch(26, n * 4));
+        uint8_t* d_rule = static_cast<uint8_t*>(scratch(27, n));
+        parse(hb.fb, option, mode, NEXG_OUT_RECORD, d_recs);
+        const uint64_t k = select(hb.fb, d_recs, filter, d_idx, d_off, d_len, d_rule);
+        nexg_frames sel = hb.fb;
+        sel.offsets = d_off;
+        sel.lengths = d_len;
+        sel.count = k;
+        sel.hints = NEXG_FRAMES_MONOTONE;
+        uint64_t* d_go = static_cast<uint64_t*>(scratch(28, (k + 1) * 8));
+        uint32_t* d_gl = static_cast<uint32_t*>(scratch(29, k * 4));
+        const uint64_t total = gather_plan(sel, align, d_go, d_gl);
+        uint8_t* d_data = static_cast<uint8_t*>(scratch(30, total));
+        gather(sel, d_go, d_data, total);
+        nexg_record* d_rsel = static_cast<nexg_record*>(scratch(31, k * 64));
+        gather_rows(d_recs, 64, n, d_idx, k, d_rsel);
+        out.index.resize(k);
+        out.rule.resize(k);
+        out.records.resize(k);
+        out.offsets.resize(k + 1);
+        out.lengths.resize(k);
+        out.data.resize(total);
+        check_hip(hipMemcpyAsync(out.offsets.data(), d_go, (k + 1) * 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        if (k) {
+            check_hip(hipMemcpyAsync(out.index.data(), d_idx, k * 4, hipMemcpyDeviceToHost, stream_), "D2H");
+            check_hip(hipMemcpyAsync(out.rule.data(), d_rule, k, hipMemcpyDeviceToHost, stream_), "D2H");
+            check_hip(hipMemcpyAsync(out.records.data(), d_rsel, k * 64, hipMemcpyDeviceToHost, stream_), "D2H");
+            check_hip(hipMemcpyAsync(out.lengths.data(), d_gl, k * 4, hipMemcpyDeviceToHost, stream_), "D2H");
+        }
+        if (total) check_hip(hipMemcpyAsync(out.data.data(), d_data, total, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
         return out;
     }
 

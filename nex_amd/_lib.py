@@ -53,6 +53,12 @@ def load():
         "nexg_decap_select": (I, [P, P, P, P, U64, U32, P, P, P, P, P, U64, P]),
         "nexg_dns_batch": (I, [P, ctypes.POINTER(abi.Frames), P, ctypes.POINTER(abi.DnsOption), P, P, P]),
         "nexg_dns_entries": (I, [P, ctypes.POINTER(abi.Frames), P, P, P, U64, P]),
+        "nexg_filter_check": (I, [ctypes.POINTER(abi.FilterC)]),
+        "nexg_select_batch": (I, [P, ctypes.POINTER(abi.Frames), P, ctypes.POINTER(abi.FilterC), P, P, P, P, P, P, U64,
+                                  P]),
+        "nexg_gather_plan": (I, [P, ctypes.POINTER(abi.Frames), U32, P, P, P, U64, P]),
+        "nexg_gather_frames": (I, [P, ctypes.POINTER(abi.Frames), P, P, U64, P]),
+        "nexg_gather_rows": (I, [P, P, U32, U64, P, U64, P, P]),
         "nexg_build_udp4_batch": (I, [P, ctypes.POINTER(abi.Udp4Build), P, U32, P]),
         "nexg_build_udp4_tuples": (I, [P, ctypes.POINTER(abi.Udp4Build), P, P, U32, P]),
         "nexg_build_udp6_batch": (I, [P, ctypes.POINTER(abi.Udp6Build), P, U32, P]),

@@ -438,16 +438,60 @@ def dns_tile_first_bytes(count):
     """nexg_dns_tile_first_bytes: bytes of nexg_dns_batch's tile_first."""
     return 8 * ((int(count) + 255) // 256 + 1)
 
+# frame selection by rule and gather (nexg_select_batch / nexg_gather_*; an
+# extension: the reference has no filter)
+RULE_PROTO, RULE_SRC_PORT, RULE_DST_PORT, RULE_ANY_PORT = 0x1, 0x2, 0x4, 0x8
+RULE_SRC_ADDR, RULE_DST_ADDR, RULE_ANY_ADDR = 0x10, 0x20, 0x40
+RULE_TCP_FLAGS, RULE_LENGTH = 0x80, 0x100
+RULE_ALL = 0x1FF
+FILTER_INVERT = 0x1
+FILTER_MAX_RULES = 16
+RULE_NONE = 0xFF  # out_rule under FILTER_INVERT
+GATHER_ALIGNS = (1, 4, 8, 16)
+GATHER_ROW_BYTES = (4, 8, 16, 32, 64)
+
+
+class RuleC(ctypes.Structure):
+    """struct nexg_rule"""
+    _fields_ = [("flags_mask", ctypes.c_uint32), ("flags_value", ctypes.c_uint32), ("tests", ctypes.c_uint32),
+                ("ip_proto", ctypes.c_uint8), ("tcp_mask", ctypes.c_uint8), ("tcp_value", ctypes.c_uint8),
+                ("family", ctypes.c_uint8), ("src_bits", ctypes.c_uint8), ("dst_bits", ctypes.c_uint8),
+                ("reserved", ctypes.c_uint16), ("sport_lo", ctypes.c_uint16), ("sport_hi", ctypes.c_uint16),
+                ("dport_lo", ctypes.c_uint16), ("dport_hi", ctypes.c_uint16), ("len_lo", ctypes.c_uint16),
+                ("len_hi", ctypes.c_uint16), ("src", ctypes.c_uint8 * 16), ("dst", ctypes.c_uint8 * 16)]
+
+
+class FilterC(ctypes.Structure):
+    """struct nexg_filter"""
+    _fields_ = [("n_rules", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("rules", RuleC * FILTER_MAX_RULES)]
+
+
+assert ctypes.sizeof(RuleC) == 64 and ctypes.sizeof(FilterC) == 1032
+
+
+def select_workspace(count):
+    """nexg_select_workspace: bytes of nexg_select_batch's workspace."""
+    tiles = (int(count) + 255) // 256
+    return 4 * ((tiles + 255) // 256 * 256) + 16
+
+
+def gather_plan_workspace(count):
+    """nexg_gather_plan_workspace: bytes of nexg_gather_plan's workspace."""
+    tiles = (int(count) + 255) // 256
+    return 8 * ((tiles + 255) // 256 * 256) + 16
+
 
 #: static inline helpers of include/nexg.h (header-only, not exported)
 HEADER_INLINE = ("nexg_sparse_decode", "nexg_grouped_code", "nexg_grouped_exc_slot", "nexg_offsets32_bases",
-                 "nexg_offsets32_bytes", "nexg_decap_select_workspace", "nexg_dns_tile_first_bytes")
+                 "nexg_offsets32_bytes", "nexg_decap_select_workspace", "nexg_dns_tile_first_bytes",
+                 "nexg_select_workspace", "nexg_gather_plan_workspace")
 
 #: every symbol include/nexg.h declares (tests check the .so exports them)
 EXPORTED_SYMBOLS = (
     "nexg_abi_version", "nexg_strerror", "nexg_ctx_create", "nexg_ctx_destroy",
     "nexg_ctx_last_error", "nexg_ctx_cu_count", "nexg_parse_batch", "nexg_checksum_batch", "nexg_decode_options", "nexg_probe_stream",
     "nexg_decap_batch", "nexg_decap_select", "nexg_dns_batch", "nexg_dns_entries",
+    "nexg_filter_check", "nexg_select_batch", "nexg_gather_plan", "nexg_gather_frames", "nexg_gather_rows",
     "nexg_probe_span_clock", "nexg_probe_latency",
     "nexg_sparse_expand", "nexg_grouped_expand", "nexg_recompute_checksums_batch",
     "nexg_rx_config_default", "nexg_rx_open", "nexg_rx_next_batch", "nexg_rx_stats", "nexg_rx_close",

@@ -346,6 +346,93 @@ int nexg_dns_entries(nexg_ctx* ctx, const nexg_frames* frames, const nexg_dns* d
                       NEXG_ELAUNCH);
 }
 
+int nexg_filter_check(const nexg_filter* filter) {
+    return nexg::prepare_filter(filter, nullptr) ? NEXG_EINVAL : NEXG_OK;
+}
+
+int nexg_select_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records,
+                      const nexg_filter* filter, uint32_t* out_index, uint64_t* out_off, uint32_t* out_len,
+                      uint8_t* out_rule, uint64_t* out_count, void* workspace, uint64_t workspace_bytes,
+                      void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    nexg::SelFilter f;
+    if (const char* why = nexg::prepare_filter(filter, &f)) return fail(ctx, NEXG_EINVAL, "select: %s", why);
+    const uint64_t count = frames->count;
+    if (count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "select: more than 2^32 - 1 frames%s", nullptr);
+    if (!out_count) return fail(ctx, NEXG_EINVAL, "NULL out_count%s", nullptr);
+    if (count && (!records || !out_index || !out_off || !out_len || !workspace))
+        return fail(ctx, NEXG_EINVAL, "NULL records, output or workspace%s", nullptr);
+    if (count && workspace_bytes < nexg_select_workspace(count))
+        return fail(ctx, NEXG_EINVAL, "select: workspace smaller than nexg_select_workspace%s", nullptr);
+    if ((reinterpret_cast<uint64_t>(records) & 15u) != 0 ||
+        ((reinterpret_cast<uint64_t>(out_off) | reinterpret_cast<uint64_t>(out_count)) & 7u) != 0 ||
+        ((reinterpret_cast<uint64_t>(out_index) | reinterpret_cast<uint64_t>(out_len) |
+          reinterpret_cast<uint64_t>(workspace)) & 3u) != 0)
+        return fail(ctx, NEXG_EINVAL, "misaligned records, output or workspace%s", nullptr);
+    const nexg::ParseArgs a = to_args(frames);
+    DeviceGuard g(ctx);
+    return hip_status(ctx, nexg::launch_select(a, records, f, out_index, out_off, out_len, out_rule, out_count,
+                                               static_cast<uint32_t*>(workspace), static_cast<hipStream_t>(stream)),
+                      NEXG_ELAUNCH);
+}
+
+int nexg_gather_plan(nexg_ctx* ctx, const nexg_frames* sel, uint32_t align, uint64_t* out_offsets,
+                     uint32_t* out_len, void* workspace, uint64_t workspace_bytes, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(sel)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    if (align != 1 && align != 4 && align != 8 && align != 16)
+        return fail(ctx, NEXG_EINVAL, "gather_plan: align must be 1, 4, 8 or 16%s", nullptr);
+    const uint64_t count = sel->count;
+    if (count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "gather_plan: more than 2^32 - 1 frames%s", nullptr);
+    if (!out_offsets) return fail(ctx, NEXG_EINVAL, "NULL out_offsets%s", nullptr);
+    if (count && !workspace) return fail(ctx, NEXG_EINVAL, "NULL workspace%s", nullptr);
+    if (count && workspace_bytes < nexg_gather_plan_workspace(count))
+        return fail(ctx, NEXG_EINVAL, "gather_plan: workspace smaller than nexg_gather_plan_workspace%s", nullptr);
+    if (((reinterpret_cast<uint64_t>(out_offsets) | reinterpret_cast<uint64_t>(workspace)) & 7u) != 0 ||
+        (reinterpret_cast<uint64_t>(out_len) & 3u) != 0)
+        return fail(ctx, NEXG_EINVAL, "misaligned output or workspace%s", nullptr);
+    const nexg::ParseArgs a = to_args(sel);
+    DeviceGuard g(ctx);
+    return hip_status(ctx, nexg::launch_gather_plan(a, align, out_offsets, out_len, static_cast<uint64_t*>(workspace),
+                                                    static_cast<hipStream_t>(stream)),
+                      NEXG_ELAUNCH);
+}
+
+int nexg_gather_frames(nexg_ctx* ctx, const nexg_frames* sel, const uint64_t* out_offsets, uint8_t* out_data,
+                       uint64_t out_cap, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(sel)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    if (sel->count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "gather_frames: more than 2^32 - 1 frames%s", nullptr);
+    if (sel->count && !out_offsets) return fail(ctx, NEXG_EINVAL, "NULL out_offsets%s", nullptr);
+    if (out_cap && !out_data) return fail(ctx, NEXG_EINVAL, "NULL out_data with a nonzero capacity%s", nullptr);
+    if ((reinterpret_cast<uint64_t>(out_offsets) & 7u) != 0 || (reinterpret_cast<uint64_t>(out_data) & 15u) != 0)
+        return fail(ctx, NEXG_EINVAL, "misaligned out_offsets or out_data%s", nullptr);
+    const nexg::ParseArgs a = to_args(sel);
+    DeviceGuard g(ctx);
+    return hip_status(ctx, nexg::launch_gather_frames(a, out_offsets, out_data, out_cap,
+                                                      static_cast<hipStream_t>(stream)),
+                      NEXG_ELAUNCH);
+}
+
+int nexg_gather_rows(nexg_ctx* ctx, const void* rows, uint32_t row_bytes, uint64_t rows_count,
+                     const uint32_t* index, uint64_t n, void* out, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (row_bytes != 4 && row_bytes != 8 && row_bytes != 16 && row_bytes != 32 && row_bytes != 64)
+        return fail(ctx, NEXG_EINVAL, "gather_rows: row_bytes must be 4, 8, 16, 32 or 64%s", nullptr);
+    if (n > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "gather_rows: more than 2^32 - 1 rows%s", nullptr);
+    if (n && (!index || !out || (rows_count && !rows)))
+        return fail(ctx, NEXG_EINVAL, "NULL rows, index or output%s", nullptr);
+    const uint64_t am = (row_bytes < 16u ? row_bytes : 16u) - 1u;
+    if (((reinterpret_cast<uint64_t>(rows) | reinterpret_cast<uint64_t>(out)) & am) != 0 ||
+        (reinterpret_cast<uint64_t>(index) & 3u) != 0)
+        return fail(ctx, NEXG_EINVAL, "misaligned rows, index or output%s", nullptr);
+    DeviceGuard g(ctx);
+    return hip_status(ctx, nexg::launch_gather_rows(rows, row_bytes, rows_count, index, n, out,
+                                                    static_cast<hipStream_t>(stream)),
+                      NEXG_ELAUNCH);
+}
+
 int nexg_probe_stream(nexg_ctx* ctx, const void* data, uint64_t bytes, uint32_t out_per_64,
                       void* out, void* stream) {
     if (!ctx) return NEXG_EINVAL;

@@ -117,6 +117,33 @@ hipError_t launch_dns(const ParseArgs& a, const nexg_record* recs, uint32_t any_
 hipError_t launch_dns_entries(const ParseArgs& a, const nexg_dns* dns, const uint64_t* tile_first,
                               nexg_dns_entry* entries, uint64_t cap, hipStream_t s);
 
+// nexg_select_batch / nexg_gather_* (nexg_select.hip). The filter travels as a
+// kernel argument in the form the kernel tests with: addresses as big-endian
+// word values with their prefix masks applied, ranges packed lo | hi << 16.
+struct SelRule {  // 96 bytes
+    uint32_t flags_mask, flags_value, tests;
+    uint32_t misc;  // ip_proto | tcp_mask << 8 | tcp_value << 16 | family << 24
+    uint32_t sport, dport, length, pad;
+    uint32_t src[4], src_mask[4], dst[4], dst_mask[4];
+};
+struct SelFilter {
+    uint32_t n_rules, invert;
+    uint32_t need;  // kSelNeed*: which record dwords / frame bytes some rule reads
+    uint32_t pad;
+    SelRule rule[NEXG_FILTER_MAX_RULES];
+};
+// nullptr when the filter is valid (then *out, if given, is filled), else what is wrong with it
+const char* prepare_filter(const nexg_filter* f, SelFilter* out);
+hipError_t launch_select(const ParseArgs& a, const nexg_record* recs, const SelFilter& f, uint32_t* out_index,
+                         uint64_t* out_off, uint32_t* out_len, uint8_t* out_rule, uint64_t* out_count,
+                         uint32_t* tile_count, hipStream_t s);
+hipError_t launch_gather_plan(const ParseArgs& a, uint32_t align, uint64_t* out_offsets, uint32_t* out_len,
+                              uint64_t* tile_sum, hipStream_t s);
+hipError_t launch_gather_frames(const ParseArgs& a, const uint64_t* out_offsets, uint8_t* out_data, uint64_t out_cap,
+                                hipStream_t s);
+hipError_t launch_gather_rows(const void* rows, uint32_t row_bytes, uint64_t rows_count, const uint32_t* index,
+                              uint64_t n, void* out, hipStream_t s);
+
 hipError_t launch_probe_stream(const uint8_t* data, uint64_t tiles, uint32_t mode, void* out, hipStream_t s);
 hipError_t launch_probe_latency(uint32_t* buf, uint32_t lines, uint32_t start, uint32_t steps, uint32_t loaded_wgs,
                                 uint32_t rounds, uint64_t* out, hipStream_t s);

@@ -340,6 +340,95 @@ class Engine:
         k = int(cnt.item())  # waits for the kernels
         return idx[:k], FrameBatch(data=inner.data, count=k, offsets=off[:k], lengths=ln[:k], hints=inner.hints)
 
+    def select(self, batch: FrameBatch, records, flt, want_rule: bool = False, stream=None):
+        """Order-preserving selection of frames by rule (nexg_select_batch;
+        an extension, the reference has no filter). `records` is the uint8
+        device tensor a NEXG_OUT_RECORD parse of `batch` returned (for an
+        inner table from Engine.decap: the inner records), `flt` a
+        nex_amd.select.Filter. Returns (index, selected[, rule]): index an
+        int32 device tensor (bit patterns of u32) with the frame number of
+        each selected frame, selected a FrameBatch (offsets + lengths) over
+        the same data whose count is the selected count, rule (want_rule) a
+        uint8 device tensor with the lowest matching rule per selected frame.
+        Allocates the workspace and reads the selected count back: one
+        synchronisation of the stream.
+
+        The recipe: parse, select, compact the records, run the follow-up
+        passes on the selected table only, copy out just what matched:
+
+            rec = eng.parse(batch, out_kind=abi.OUT_RECORD)
+            idx, sel = eng.select(batch, rec, Filter([Rule.udp() & Rule.port(53)]))
+            rec_sel = eng.gather_rows(rec, 64, idx)          # records of the selected frames
+            dns, tile_first, entries, total = eng.dns(sel, rec_sel)
+            tunnels, inner = eng.decap(sel, rec_sel)
+            dense = eng.gather(sel)                          # a packed batch of the selected bytes
+        """
+        torch = _torch()
+        fc = flt.to_c()  # ValueError for what nexg_select_batch rejects
+        count = batch.count
+        n = max(count, 1)
+        dev = self.torch_device
+        idx = torch.empty(n, dtype=torch.int32, device=dev)
+        off = torch.empty(n, dtype=torch.int64, device=dev)
+        ln = torch.empty(n, dtype=torch.int32, device=dev)
+        rule = torch.empty(n, dtype=torch.uint8, device=dev) if want_rule else None
+        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        ws_bytes = abi.select_workspace(count)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        fr = batch.to_c()
+        self._check(self.lib.nexg_select_batch(self.ctx, ctypes.byref(fr), _ptr(records), ctypes.byref(fc), _ptr(idx),
+                                               _ptr(off), _ptr(ln), _ptr(rule), _ptr(cnt), _ptr(ws), ws_bytes,
+                                               self._stream(stream)))
+        k = int(cnt.item())  # waits for the kernels
+        ordered = batch.offsets is None or batch.lengths is None or bool(batch.hints & abi.FRAMES_MONOTONE)
+        sel = FrameBatch(data=batch.data, count=k, offsets=off[:k], lengths=ln[:k],
+                         hints=abi.FRAMES_MONOTONE if ordered else 0)
+        return (idx[:k], sel, rule[:k]) if want_rule else (idx[:k], sel)
+
+    def gather(self, sel: FrameBatch, align: int = 1, stream=None):
+        """Copy the frames of `sel` (usually Engine.select's table) into one
+        dense buffer (nexg_gather_plan + nexg_gather_frames). Returns a new
+        FrameBatch that owns its data: packed (offsets only) with align 1,
+        offsets + lengths with each frame's start rounded up to `align`
+        (4, 8 or 16) and the pads zero. A frame whose extent leaves the data
+        or whose length exceeds 65535 is copied as length 0. Reads the total
+        back: one synchronisation of the stream."""
+        torch = _torch()
+        if align not in abi.GATHER_ALIGNS:
+            raise ValueError("align must be 1, 4, 8 or 16")
+        dev = self.torch_device
+        n = sel.count
+        offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        ln = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if align != 1 else None
+        ws_bytes = abi.gather_plan_workspace(n)
+        ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
+        fr = sel.to_c()
+        s = self._stream(stream)
+        self._check(self.lib.nexg_gather_plan(self.ctx, ctypes.byref(fr), align, _ptr(offs), _ptr(ln), _ptr(ws),
+                                              ws_bytes, s))
+        total = int(offs[n].item())  # waits for the kernels
+        data = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+        self._check(self.lib.nexg_gather_frames(self.ctx, ctypes.byref(fr), _ptr(offs), _ptr(data), total, s))
+        return FrameBatch(data=data[:total], count=n, offsets=offs, lengths=None if ln is None else ln[:n],
+                          hints=0 if ln is None else abi.FRAMES_MONOTONE)
+
+    def gather_rows(self, rows, row_bytes: int, index, stream=None):
+        """Compact per-frame rows by a selected index (nexg_gather_rows):
+        row k of the result is rows[index[k]], zeros where index[k] is past
+        the rows. `rows` is a device tensor of whole rows of `row_bytes` (4,
+        8, 16, 32 or 64: flags words, descriptors, nexg_tunnel, nexg_dns,
+        records), `index` the int32 tensor Engine.select returned. Returns a
+        uint8 device tensor of len(index) * row_bytes bytes."""
+        torch = _torch()
+        if row_bytes not in abi.GATHER_ROW_BYTES:
+            raise ValueError("row_bytes must be 4, 8, 16, 32 or 64")
+        n = index.numel()
+        rows_count = rows.numel() * rows.element_size() // row_bytes
+        out = torch.empty(max(n, 1) * row_bytes, dtype=torch.uint8, device=self.torch_device)
+        self._check(self.lib.nexg_gather_rows(self.ctx, _ptr(rows), row_bytes, rows_count, _ptr(index), n, _ptr(out),
+                                              self._stream(stream)))
+        return out[: n * row_bytes]
+
     def dns(self, batch: FrameBatch, records, port: int = abi.DNS_PORT, any_udp: bool = False, entries_cap=None,
             stream=None):
         """Walk every DNS message of `batch` in place (nexg_dns_batch +
