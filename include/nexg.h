@@ -875,6 +875,122 @@ int nexg_gather_frames(nexg_ctx* ctx, const nexg_frames* sel, const uint64_t* ou
 int nexg_gather_rows(nexg_ctx* ctx, const void* rows, uint32_t row_bytes, uint64_t rows_count,
                      const uint32_t* index, uint64_t n, void* out, void* stream);
 
+/* ---- flow keys, RSS hash and flow-affine partition (extension) -----------------
+ * The reference has no flow notion; like the selection above this is an
+ * extension, and the text below is its whole specification
+ * (nex_amd/flow.py flow_host / partition_host restate it on the host).
+ * nexg_flow_batch gives every frame of a batch already parsed with
+ * NEXG_OUT_RECORD (any parse option; an inner table from nexg_decap_batch with
+ * its inner records works too) an 8-byte flow row: the Toeplitz RSS hash of its
+ * addresses and ports, as NICs, DPDK and the Linux drivers compute it.
+ * nexg_flow_partition splits a frame table into up to 256 buckets by that hash,
+ * stably, so that every flow lands whole in one bucket.
+ *
+ * Which frames have a flow. Only the record decides. status must be 0, and
+ * the frame needs NEXG_L_IPV4, or (without NEXG_L_IPV4) NEXG_L_IPV6 with a
+ * valid extent and l3_off + 40 <= len(i). Every other frame (ARP,
+ * Ethernet-only, an error status, a bad extent, a record whose l3_off points
+ * past its frame) gets an all-zero row.
+ *
+ * Addresses. IPv4: record.ip_src and ip_dst as four big-endian bytes each.
+ * IPv6: frame bytes [l3_off + 8, l3_off + 24) and [l3_off + 24, l3_off + 40)
+ * (the record does not carry them; the 16-B block rule of the frame batch
+ * layout applies and nothing outside the frame's own blocks is read).
+ *
+ * Ports join the key when the record has NEXG_L_TCP or NEXG_L_UDP and
+ * NEXG_FLOW_NO_PORTS is clear, except for an IPv4 frame with
+ * (ip_word & 0x3FFF) != 0 (MF set, or a fragment offset): NICs leave the ports
+ * out there as well, so all fragments of a datagram hash alike. That gives
+ * `kind` its _L4 value or the plain one. Nothing else is special-cased: an
+ * IPv6 fragment header is not detected (the parser gives such a frame no
+ * transport layer, so it hashes on its addresses), and IPv6 extension-header
+ * address options (home address, routing header) are not followed.
+ *
+ * Key bytes: source address, destination address, then src_port and dst_port
+ * as two big-endian bytes each: 8, 12, 32 or 36 bytes. Under
+ * NEXG_FLOW_SYMMETRIC the byte string (source address, src_port) is compared
+ * with (destination address, dst_port), the addresses alone when the ports are
+ * not part of the key; when the source side is greater the endpoints are
+ * exchanged before hashing and `swapped` is 1, so both directions of a
+ * conversation get one key.
+ *
+ * Hash: the Toeplitz RSS hash with a 320-bit key K. For every set bit of the
+ * key bytes, bit s counted from the most significant bit of byte 0, the 32 key
+ * bits K[s, s + 32) are XORed into the 32-bit result. 36 input bytes reach key
+ * bit 319: 40 key bytes always suffice. The default key is the Microsoft RSS
+ * verification key NEXG_FLOW_DEFAULT_KEY, so a hash computed here equals the
+ * one such hardware put in the descriptor; NEXG_FLOW_KEY takes option->key
+ * instead.
+ *
+ * NEXG_EINVAL: unknown flag bits, reserved != 0, a NULL pointer with
+ * count > 0, a misaligned pointer (records 16 B, out 8 B). count == 0 launches
+ * nothing. One kernel on `stream`. */
+#define NEXG_FLOW_SYMMETRIC 0x1u /* both directions of a conversation get one key */
+#define NEXG_FLOW_NO_PORTS 0x2u  /* 2-tuple only */
+#define NEXG_FLOW_KEY 0x4u       /* use option->key; else NEXG_FLOW_DEFAULT_KEY */
+#define NEXG_FLOW_DEFAULT_KEY                                                                     \
+    {0x6d, 0x5a, 0x56, 0xda, 0x25, 0x5b, 0x0e, 0xc2, 0x41, 0x67, 0x25, 0x3d, 0x43, 0xa3, 0x8f, 0xb0, \
+     0xd0, 0xca, 0x2b, 0xcb, 0xae, 0x7b, 0x30, 0xb4, 0x77, 0xcb, 0x2d, 0xa3, 0x80, 0x30, 0xf2, 0x0c, \
+     0x6a, 0x42, 0xb7, 0x3b, 0xbe, 0xac, 0x01, 0xfa}
+typedef struct nexg_flow_option { /* host memory; read during the call, not after it */
+    uint32_t flags;    /* NEXG_FLOW_*; unknown bits -> NEXG_EINVAL */
+    uint32_t reserved; /* must be 0 */
+    uint8_t key[40];   /* NEXG_FLOW_KEY */
+} nexg_flow_option;
+enum { NEXG_FLOW_NONE = 0, NEXG_FLOW_IPV4 = 1, NEXG_FLOW_IPV4_L4 = 2, NEXG_FLOW_IPV6 = 3, NEXG_FLOW_IPV6_L4 = 4 };
+typedef struct nexg_flow { /* 8 bytes */
+    uint32_t hash;    /* Toeplitz hash of the key bytes; 0 for NEXG_FLOW_NONE */
+    uint8_t kind;     /* NEXG_FLOW_* */
+    uint8_t proto;    /* record.ip_proto; 0 for NONE */
+    uint8_t swapped;  /* 1 when NEXG_FLOW_SYMMETRIC exchanged the endpoints */
+    uint8_t reserved; /* 0 */
+} nexg_flow;
+int nexg_flow_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records,
+                    const nexg_flow_option* option /* NULL = defaults */, nexg_flow* out /* 8-B aligned */,
+                    void* stream);
+
+/* Stable split of a frame table into `buckets` (1..256) buckets:
+ * bucket(i) = flows[i].hash % buckets (frames without a flow have hash 0 and
+ * fall into bucket 0). The output is ordered by bucket, then by frame index.
+ * bucket_first[b] (buckets + 1 entries, device memory, 8-B aligned) = the
+ * number of frames in buckets below b; bucket_first[buckets] = count. For the
+ * k-th output entry out_index[k] = i, and out_off[k] / out_len[k] (both NULL,
+ * or both given) = off(i) / len(i) exactly as nexg_select_batch stores them.
+ * For every b, {data, data_bytes, out_off + bucket_first[b], out_len +
+ * bucket_first[b], bucket_first[b + 1] - bucket_first[b]} is a frame table
+ * that parse, decap, dns, select and gather take as it stands, monotone
+ * whenever the input was packed, fixed-stride or monotone; nexg_gather_rows
+ * with out_index reorders records or any other per-frame rows to match. The
+ * output arrays have capacity `count` (out_off 8-B, out_index / out_len 4-B
+ * aligned); count must not exceed 2^32 - 1.
+ *
+ * The partition works on tiles of NEXG_FLOW_TILE = 1024 frames: a count
+ * kernel writes one histogram per tile, bucket-major (buckets x tiles u32
+ * counters), a three-kernel hierarchical scan (sums of 1024-counter chunks,
+ * a scan of the chunk sums, the add-back) turns them into the global base of
+ * every (bucket, tile) pair, and a scatter kernel recomputes each frame's
+ * stable rank inside its tile. Positions come from ballots, ranks and scans
+ * only (no atomics): a run repeats bit for bit. `flows` and the workspace are
+ * caller memory: every store is bounded by `count`, whatever they hold.
+ * workspace: device memory (8-B aligned) of at least
+ * nexg_flow_partition_workspace(count, buckets) bytes. count == 0 writes
+ * bucket_first[0..buckets] = 0 and launches nothing else. NEXG_EINVAL:
+ * buckets outside 1..256, an invalid frame table, a NULL or misaligned
+ * pointer (flows 8 B), only one of out_off / out_len NULL, a short workspace.
+ * Five kernels on `stream`. */
+#define NEXG_FLOW_TILE 1024u
+int nexg_flow_partition(nexg_ctx* ctx, const nexg_frames* frames, const nexg_flow* flows, uint32_t buckets,
+                        uint32_t* out_index, uint64_t* out_off, uint32_t* out_len, uint64_t* bucket_first,
+                        void* workspace, uint64_t workspace_bytes, void* stream);
+/* 8 B (the scan's total), one u32 per chunk of 1024 counters, then the
+ * buckets x ceil(count / 1024) counters */
+static inline uint64_t nexg_flow_partition_workspace(uint64_t count, uint32_t buckets) {
+    const uint64_t tiles = (count + NEXG_FLOW_TILE - 1u) / NEXG_FLOW_TILE;
+    const uint64_t counters = tiles * buckets;
+    const uint64_t chunks = (counters + 1023u) / 1024u;
+    return 8u + 4u * ((chunks + 1u) & ~(uint64_t)1u) + 4u * counters;
+}
+
 /* ---- calibration (not a reference entry point) ---------------------------
  * The HBM stream ceilings the parse kernels are measured against, on the
  * caller's own buffer and box: `bytes` (a multiple of 16384) read with the

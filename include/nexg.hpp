@@ -27,6 +27,10 @@
  *                           no reference counterpart (an extension): frames
  *                           picked by rules over the parsed fields, and the
  *                           gather of their bytes and rows (include/nexg.h)
+ *   FlowOption, Engine::flow / flow_partition / flow_bufs
+ *                           no reference counterpart (an extension): the
+ *                           Toeplitz RSS hash of every frame's flow key and the
+ *                           stable split of a batch into flow-affine buckets
  * The device does the parse and the checksums (nexg_parse_batch,
  * NEXG_OUT_RECORD) and the option lists (nexg_decode_options); this header
  * only reads header fields out of the frame bytes at the offsets the device
@@ -888,6 +892,29 @@ inline std::vector<uint8_t> message_bytes(const Icmpv6Packet& p) {
 }  // namespace ndp
 }  // namespace icmpv6
 
+/* ---- flow keys (extension: the reference has no flow notion) --------------- */
+
+// nexg_flow_option (include/nexg.h): which key a frame's flow row hashes.
+//   FlowOption().symmetric()        both directions of a conversation get one key
+//   FlowOption().no_ports()         addresses only
+//   FlowOption().key(bytes40)       a Toeplitz key other than the default RSS one
+struct FlowOption {
+    nexg_flow_option o{};
+    FlowOption& symmetric(bool on = true) { return set(NEXG_FLOW_SYMMETRIC, on); }
+    FlowOption& no_ports(bool on = true) { return set(NEXG_FLOW_NO_PORTS, on); }
+    FlowOption& key(const std::array<uint8_t, 40>& k) {
+        std::memcpy(o.key, k.data(), 40);
+        return set(NEXG_FLOW_KEY, true);
+    }
+    const nexg_flow_option& get() const { return o; }
+
+private:
+    FlowOption& set(uint32_t bit, bool on) {
+        o.flags = on ? o.flags | bit : o.flags & ~bit;
+        return *this;
+    }
+};
+
 /* ---- frame selection (extension: the reference has no filter) ------------- */
 
 // Builder of a nexg_filter (include/nexg.h): any / flags / udp / tcp / status /
@@ -1279,6 +1306,71 @@ class Engine {  // one nexg context on one gfx950 device, one stream
         }
         if (total) check_hip(hipMemcpyAsync(out.data.data(), d_data, total, hipMemcpyDeviceToHost, stream_), "D2H");
         check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        return out;
+    }
+
+    // A flow row per frame of a device-resident batch already parsed with
+    // NEXG_OUT_RECORD (an extension, include/nexg.h nexg_flow_batch): the
+    // Toeplitz RSS hash of the addresses and ports, the kind of key, the IP
+    // protocol. `out` is a device array of frames.count rows (8-B aligned).
+    void flow(const nexg_frames& frames, const nexg_record* records, nexg_flow* out, const FlowOption& option = {}) {
+        DeviceScope ds(device_);
+        check(nexg_flow_batch(ctx_, &frames, records, &option.get(), out, stream_), "nexg_flow_batch");
+    }
+
+    // Stable split of the batch into `buckets` (1..256) buckets by
+    // flows[i].hash % buckets (nexg_flow_partition): device arrays of capacity
+    // frames.count (out_off and out_len may both be null); returns
+    // bucket_first (buckets + 1 entries, one stream synchronisation). Bucket b
+    // is {frames.data, frames.data_bytes, out_off + first[b], out_len +
+    // first[b], first[b + 1] - first[b]}: parse, decap, dns, select and gather
+    // take it as it stands, with gather_rows(records, 64, ..., out_index, ...)
+    // for the records in the same order.
+    std::vector<uint64_t> flow_partition(const nexg_frames& frames, const nexg_flow* flows, uint32_t buckets,
+                                         uint32_t* out_index, uint64_t* out_off, uint32_t* out_len) {
+        DeviceScope ds(device_);
+        if (buckets < 1 || buckets > 256) throw Error("flow_partition: buckets must be 1..256");
+        const uint64_t wsb = nexg_flow_partition_workspace(frames.count, buckets);
+        void* ws = scratch(32, wsb);
+        uint64_t* d_first = static_cast<uint64_t*>(scratch(33, 8 * (buckets + 1)));
+        check(nexg_flow_partition(ctx_, &frames, flows, buckets, out_index, out_off, out_len, d_first, ws, wsb, stream_),
+              "nexg_flow_partition");
+        std::vector<uint64_t> first(buckets + 1);
+        check_hip(hipMemcpyAsync(first.data(), d_first, 8 * (buckets + 1), hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        return first;
+    }
+
+    // parse (NEXG_OUT_RECORD) + flow + flow_partition of host frames: every
+    // frame's flow row and bucket, and the frame numbers in bucket order
+    struct Flows {
+        std::vector<nexg_flow> flows;       // per frame
+        std::vector<uint32_t> bucket;       // per frame
+        std::vector<uint32_t> index;        // frame numbers ordered by bucket, then by frame
+        std::vector<uint64_t> bucket_first; // buckets + 1
+    };
+    Flows flow_bufs(const std::vector<std::vector<uint8_t>>& frames, uint32_t buckets, const FlowOption& fopt = {},
+                    ParseOption option = {}, ParseMode mode = ParseMode::Lenient) {
+        DeviceScope ds(device_);
+        const uint64_t n = frames.size();
+        Flows out;
+        out.bucket_first.assign(buckets + 1, 0);
+        if (n == 0) return out;
+        HostBatch hb(*this, frames);
+        nexg_record* d_recs = static_cast<nexg_record*>(scratch(3, n * 64));
+        nexg_flow* d_flows = static_cast<nexg_flow*>(scratch(34, n * 8));
+        uint32_t* d_idx = static_cast<uint32_t*>(scratch(24, n * 4));
+        parse(hb.fb, option, mode, NEXG_OUT_RECORD, d_recs);
+        flow(hb.fb, d_recs, d_flows, fopt);
+        out.bucket_first = flow_partition(hb.fb, d_flows, buckets, d_idx, nullptr, nullptr);
+        out.flows.resize(n);
+        out.index.resize(n);
+        out.bucket.resize(n);
+        check_hip(hipMemcpyAsync(out.flows.data(), d_flows, n * 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipMemcpyAsync(out.index.data(), d_idx, n * 4, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        for (uint32_t b = 0; b < buckets; b++)
+            for (uint64_t k = out.bucket_first[b]; k < out.bucket_first[b + 1]; k++) out.bucket[out.index[k]] = b;
         return out;
     }
 

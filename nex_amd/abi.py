@@ -481,10 +481,36 @@ def gather_plan_workspace(count):
     return 8 * ((tiles + 255) // 256 * 256) + 16
 
 
+# flow keys, RSS hash and flow-affine partition (nexg_flow_batch /
+# nexg_flow_partition; an extension: the reference has no flow notion)
+FLOW_SYMMETRIC, FLOW_NO_PORTS, FLOW_KEY = 0x1, 0x2, 0x4
+FLOW_ALL = 0x7
+FLOW_NONE, FLOW_IPV4, FLOW_IPV4_L4, FLOW_IPV6, FLOW_IPV6_L4 = 0, 1, 2, 3, 4
+FLOW_TILE = 1024  # NEXG_FLOW_TILE: frames per partition tile
+FLOW_MAX_BUCKETS = 256
+FLOW_DTYPE = np.dtype([("hash", "<u4"), ("kind", "u1"), ("proto", "u1"), ("swapped", "u1"), ("reserved", "u1")])
+assert FLOW_DTYPE.itemsize == 8
+
+
+class FlowOptionC(ctypes.Structure):
+    """struct nexg_flow_option"""
+    _fields_ = [("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("key", ctypes.c_uint8 * 40)]
+
+
+assert ctypes.sizeof(FlowOptionC) == 48
+
+
+def flow_partition_workspace(count, buckets):
+    """nexg_flow_partition_workspace: bytes of nexg_flow_partition's workspace."""
+    counters = (int(count) + FLOW_TILE - 1) // FLOW_TILE * int(buckets)
+    chunks = (counters + 1023) // 1024
+    return 8 + 4 * ((chunks + 1) & ~1) + 4 * counters
+
+
 #: static inline helpers of include/nexg.h (header-only, not exported)
 HEADER_INLINE = ("nexg_sparse_decode", "nexg_grouped_code", "nexg_grouped_exc_slot", "nexg_offsets32_bases",
                  "nexg_offsets32_bytes", "nexg_decap_select_workspace", "nexg_dns_tile_first_bytes",
-                 "nexg_select_workspace", "nexg_gather_plan_workspace")
+                 "nexg_select_workspace", "nexg_gather_plan_workspace", "nexg_flow_partition_workspace")
 
 #: every symbol include/nexg.h declares (tests check the .so exports them)
 EXPORTED_SYMBOLS = (
@@ -492,6 +518,7 @@ EXPORTED_SYMBOLS = (
     "nexg_ctx_last_error", "nexg_ctx_cu_count", "nexg_parse_batch", "nexg_checksum_batch", "nexg_decode_options", "nexg_probe_stream",
     "nexg_decap_batch", "nexg_decap_select", "nexg_dns_batch", "nexg_dns_entries",
     "nexg_filter_check", "nexg_select_batch", "nexg_gather_plan", "nexg_gather_frames", "nexg_gather_rows",
+    "nexg_flow_batch", "nexg_flow_partition",
     "nexg_probe_span_clock", "nexg_probe_latency",
     "nexg_sparse_expand", "nexg_grouped_expand", "nexg_recompute_checksums_batch",
     "nexg_rx_config_default", "nexg_rx_open", "nexg_rx_next_batch", "nexg_rx_stats", "nexg_rx_close",

@@ -433,6 +433,58 @@ int nexg_gather_rows(nexg_ctx* ctx, const void* rows, uint32_t row_bytes, uint64
                       NEXG_ELAUNCH);
 }
 
+int nexg_flow_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records,
+                    const nexg_flow_option* option, nexg_flow* out, void* stream) {
+    static const uint8_t default_key[40] = NEXG_FLOW_DEFAULT_KEY;
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    uint32_t flags = 0u;
+    const uint8_t* key = default_key;
+    if (option) {
+        if (option->reserved != 0) return fail(ctx, NEXG_EINVAL, "flow option: reserved must be 0%s", nullptr);
+        if ((option->flags & ~(NEXG_FLOW_SYMMETRIC | NEXG_FLOW_NO_PORTS | NEXG_FLOW_KEY)) != 0)
+            return fail(ctx, NEXG_EINVAL, "flow option: unknown flag bits%s", nullptr);
+        flags = option->flags;
+        if (flags & NEXG_FLOW_KEY) key = option->key;
+    }
+    if (frames->count && (!records || !out)) return fail(ctx, NEXG_EINVAL, "NULL records or output%s", nullptr);
+    if ((reinterpret_cast<uint64_t>(records) & 15u) != 0 || (reinterpret_cast<uint64_t>(out) & 7u) != 0)
+        return fail(ctx, NEXG_EINVAL, "misaligned records or output%s", nullptr);
+    nexg::FlowKey k;
+    for (uint32_t i = 0; i < 10; i++)
+        k.w[i] = (uint32_t)key[4 * i] << 24 | (uint32_t)key[4 * i + 1] << 16 | (uint32_t)key[4 * i + 2] << 8 |
+                 (uint32_t)key[4 * i + 3];
+    const nexg::ParseArgs a = to_args(frames);
+    DeviceGuard g(ctx);
+    return hip_status(ctx, nexg::launch_flow(a, records, flags, k, out, static_cast<hipStream_t>(stream)), NEXG_ELAUNCH);
+}
+
+int nexg_flow_partition(nexg_ctx* ctx, const nexg_frames* frames, const nexg_flow* flows, uint32_t buckets,
+                        uint32_t* out_index, uint64_t* out_off, uint32_t* out_len, uint64_t* bucket_first,
+                        void* workspace, uint64_t workspace_bytes, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    if (buckets < 1u || buckets > 256u) return fail(ctx, NEXG_EINVAL, "flow_partition: buckets must be 1..256%s", nullptr);
+    const uint64_t count = frames->count;
+    if (count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "flow_partition: more than 2^32 - 1 frames%s", nullptr);
+    if (!bucket_first) return fail(ctx, NEXG_EINVAL, "NULL bucket_first%s", nullptr);
+    if ((out_off == nullptr) != (out_len == nullptr))
+        return fail(ctx, NEXG_EINVAL, "flow_partition: out_off and out_len go together%s", nullptr);
+    if (count && (!flows || !out_index || !workspace))
+        return fail(ctx, NEXG_EINVAL, "NULL flows, output or workspace%s", nullptr);
+    if (count && workspace_bytes < nexg_flow_partition_workspace(count, buckets))
+        return fail(ctx, NEXG_EINVAL, "flow_partition: workspace smaller than nexg_flow_partition_workspace%s", nullptr);
+    if (((reinterpret_cast<uint64_t>(flows) | reinterpret_cast<uint64_t>(out_off) |
+          reinterpret_cast<uint64_t>(bucket_first) | reinterpret_cast<uint64_t>(workspace)) & 7u) != 0 ||
+        ((reinterpret_cast<uint64_t>(out_index) | reinterpret_cast<uint64_t>(out_len)) & 3u) != 0)
+        return fail(ctx, NEXG_EINVAL, "misaligned flows, output or workspace%s", nullptr);
+    const nexg::ParseArgs a = to_args(frames);
+    DeviceGuard g(ctx);
+    return hip_status(ctx, nexg::launch_flow_partition(a, flows, buckets, out_index, out_off, out_len, bucket_first,
+                                                       workspace, static_cast<hipStream_t>(stream)),
+                      NEXG_ELAUNCH);
+}
+
 int nexg_probe_stream(nexg_ctx* ctx, const void* data, uint64_t bytes, uint32_t out_per_64,
                       void* out, void* stream) {
     if (!ctx) return NEXG_EINVAL;

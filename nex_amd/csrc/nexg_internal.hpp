@@ -144,6 +144,18 @@ hipError_t launch_gather_frames(const ParseArgs& a, const uint64_t* out_offsets,
 hipError_t launch_gather_rows(const void* rows, uint32_t row_bytes, uint64_t rows_count, const uint32_t* index,
                               uint64_t n, void* out, hipStream_t s);
 
+// nexg_flow_batch / nexg_flow_partition (nexg_flow.hip). The Toeplitz key
+// travels as a kernel argument: its 40 bytes as ten big-endian word values.
+// workspace: as nexg_flow_partition_workspace lays it out.
+struct FlowKey {
+    uint32_t w[10];
+};
+hipError_t launch_flow(const ParseArgs& a, const nexg_record* recs, uint32_t opt, const FlowKey& key, nexg_flow* out,
+                       hipStream_t s);
+hipError_t launch_flow_partition(const ParseArgs& a, const nexg_flow* flows, uint32_t buckets, uint32_t* out_index,
+                                 uint64_t* out_off, uint32_t* out_len, uint64_t* bucket_first, void* workspace,
+                                 hipStream_t s);
+
 hipError_t launch_probe_stream(const uint8_t* data, uint64_t tiles, uint32_t mode, void* out, hipStream_t s);
 hipError_t launch_probe_latency(uint32_t* buf, uint32_t lines, uint32_t start, uint32_t steps, uint32_t loaded_wgs,
                                 uint32_t rounds, uint64_t* out, hipStream_t s);

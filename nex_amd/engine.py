@@ -58,6 +58,7 @@ class FrameBatch:
     offsets: Optional[object] = None
     lengths: Optional[object] = None
     hints: int = 0  # abi.FRAMES_* (nexg_frames.hints)
+    bucket_hints: int = 0  # Engine.flow_partition's table: the hints of each bucket's view (Engine.flow_bucket)
 
     def to_c(self):
         return abi.Frames(
@@ -428,6 +429,83 @@ class Engine:
         self._check(self.lib.nexg_gather_rows(self.ctx, _ptr(rows), row_bytes, rows_count, _ptr(index), n, _ptr(out),
                                               self._stream(stream)))
         return out[: n * row_bytes]
+
+    def flow(self, batch: FrameBatch, records, option=None, stream=None):
+        """A flow row per frame (nexg_flow_batch; an extension, the reference
+        has no flow notion): the Toeplitz RSS hash of the frame's addresses
+        and ports as NICs compute it, with the kind of key, the IP protocol
+        and whether FlowOption(symmetric=True) exchanged the endpoints.
+        `records` is the uint8 device tensor a NEXG_OUT_RECORD parse of
+        `batch` returned (for an inner table from Engine.decap: the inner
+        records), `option` a nex_amd.flow.FlowOption. Returns a uint8 device
+        tensor holding nexg_flow[count] (abi.FLOW_DTYPE); frames without an
+        IP layer or with an error status have an all-zero row.
+
+        The recipe for handing each flow to one worker:
+
+            rec = eng.parse(batch, out_kind=abi.OUT_RECORD)
+            flows = eng.flow(batch, rec, FlowOption(symmetric=True))
+            index, table, first = eng.flow_partition(batch, flows, 8)
+            rec_by_bucket = eng.gather_rows(rec, 64, index)
+            for b in range(8):
+                part = eng.flow_bucket(table, first, b)      # a FrameBatch view, no copy
+                rec_b = rec_by_bucket[first[b] * 64: first[b + 1] * 64]
+        """
+        from .flow import FlowOption
+        torch = _torch()
+        fo = (option if option is not None else FlowOption()).to_c()  # ValueError for what nexg_flow_batch rejects
+        out = torch.empty(max(batch.count, 1) * 8, dtype=torch.uint8, device=self.torch_device)
+        fr = batch.to_c()
+        self._check(self.lib.nexg_flow_batch(self.ctx, ctypes.byref(fr), _ptr(records), ctypes.byref(fo), _ptr(out),
+                                             self._stream(stream)))
+        return out[: batch.count * 8]
+
+    def flow_partition(self, batch: FrameBatch, flows, buckets: int, stream=None):
+        """Stable split of `batch` into `buckets` (1..256) buckets by
+        flows[i].hash % buckets (nexg_flow_partition): every flow lands whole
+        in one bucket, frames keep their order inside a bucket, frames without
+        a flow go to bucket 0. `flows` is the tensor Engine.flow returned.
+        Returns (index, table, bucket_first): index an int32 device tensor
+        (bit patterns of u32) with the frame number of each output entry,
+        table a FrameBatch (offsets + lengths) of `count` frames in bucket
+        order over the same data, bucket_first a host int64 array of
+        buckets + 1 entries (bucket b is entries bucket_first[b] to
+        bucket_first[b + 1]; Engine.flow_bucket gives it as a batch).
+        Engine.gather_rows with index reorders records or any other per-frame
+        rows to match. Allocates the workspace and reads bucket_first back:
+        one synchronisation of the stream."""
+        torch = _torch()
+        if not 1 <= int(buckets) <= abi.FLOW_MAX_BUCKETS:
+            raise ValueError("buckets must be 1..256")
+        count = batch.count
+        n = max(count, 1)
+        dev = self.torch_device
+        idx = torch.empty(n, dtype=torch.int32, device=dev)
+        off = torch.empty(n, dtype=torch.int64, device=dev)
+        ln = torch.empty(n, dtype=torch.int32, device=dev)
+        first = torch.empty(buckets + 1, dtype=torch.int64, device=dev)
+        ws_bytes = abi.flow_partition_workspace(count, buckets)
+        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+        fr = batch.to_c()
+        self._check(self.lib.nexg_flow_partition(self.ctx, ctypes.byref(fr), _ptr(flows), int(buckets), _ptr(idx),
+                                                 _ptr(off), _ptr(ln), _ptr(first), _ptr(ws), ws_bytes,
+                                                 self._stream(stream)))
+        host_first = first.cpu().numpy()  # waits for the kernels
+        ordered = batch.offsets is None or batch.lengths is None or bool(batch.hints & abi.FRAMES_MONOTONE)
+        # monotone inside each bucket (Engine.flow_bucket's views), not across bucket boundaries
+        table = FrameBatch(data=batch.data, count=count, offsets=off[:count], lengths=ln[:count],
+                           hints=abi.FRAMES_MONOTONE if ordered and buckets == 1 else 0,
+                           bucket_hints=abi.FRAMES_MONOTONE if ordered else 0)
+        return idx[:count], table, host_first
+
+    @staticmethod
+    def flow_bucket(table: FrameBatch, bucket_first, b: int) -> FrameBatch:
+        """Bucket `b` of Engine.flow_partition's table as a FrameBatch view
+        over the same data and the same offset / length tensors (nothing is
+        copied), ready for parse, decap, dns, select and gather."""
+        lo, hi = int(bucket_first[b]), int(bucket_first[b + 1])
+        return FrameBatch(data=table.data, count=hi - lo, offsets=table.offsets[lo:hi], lengths=table.lengths[lo:hi],
+                          hints=table.bucket_hints | table.hints)
 
     def dns(self, batch: FrameBatch, records, port: int = abi.DNS_PORT, any_udp: bool = False, entries_cap=None,
             stream=None):

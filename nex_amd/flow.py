@@ -1,0 +1,134 @@
+"""Flow keys, the Toeplitz RSS hash and the flow-affine partition
+(nexg_flow_batch / nexg_flow_partition, include/nexg.h; an extension: the
+reference has no flow notion).
+
+FlowOption is the host form of struct nexg_flow_option. toeplitz, flow_host
+and partition_host restate the header's specification in plain Python: the
+GPU kernels are tested against them, and they are themselves pinned by the
+published RSS verification vectors (tests/golden/flow_vectors.json)."""
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import abi
+
+#: the Microsoft RSS verification key (NEXG_FLOW_DEFAULT_KEY)
+DEFAULT_KEY = bytes.fromhex("6d5a56da255b0ec24167253d43a38fb0d0ca2bcbae7b30b477cb2da38030f20c6a42b73bbeac01fa")
+
+
+@dataclass
+class FlowOption:
+    """struct nexg_flow_option. symmetric: both directions of a conversation
+    get one key; ports=False: addresses only; key: 40 bytes instead of
+    DEFAULT_KEY. `flags` / `reserved` set the raw fields (tests of what the
+    library rejects)."""
+    symmetric: bool = False
+    ports: bool = True
+    key: Optional[bytes] = None
+    flags: Optional[int] = None  # raw nexg_flow_option.flags; None = from the fields above
+    reserved: int = 0
+
+    def raw_flags(self) -> int:
+        if self.flags is not None:
+            return self.flags
+        return ((abi.FLOW_SYMMETRIC if self.symmetric else 0) | (0 if self.ports else abi.FLOW_NO_PORTS) |
+                (abi.FLOW_KEY if self.key is not None else 0))
+
+    def the_key(self) -> bytes:
+        return DEFAULT_KEY if not self.raw_flags() & abi.FLOW_KEY or self.key is None else bytes(self.key)
+
+    def validate(self) -> "FlowOption":
+        if self.raw_flags() & ~abi.FLOW_ALL:
+            raise ValueError("flow option: unknown flag bits")
+        if self.reserved:
+            raise ValueError("flow option: reserved must be 0")
+        if self.key is not None and len(self.key) != 40:
+            raise ValueError("flow option: the key is 40 bytes")
+        return self
+
+    def to_c(self, validate=True) -> abi.FlowOptionC:
+        if validate:
+            self.validate()
+        c = abi.FlowOptionC()
+        c.flags = self.raw_flags() & 0xFFFFFFFF
+        c.reserved = self.reserved & 0xFFFFFFFF
+        if self.key is not None:
+            c.key[:] = list(bytes(self.key)[:40].ljust(40, b"\0"))
+        return c
+
+
+def toeplitz(data: bytes, key: bytes = DEFAULT_KEY) -> int:
+    """The Toeplitz RSS hash: for every set bit s of `data` (bit 0 = the most
+    significant bit of byte 0) XOR in the 32 key bits K[s, s + 32)."""
+    nbits = 8 * len(key)
+    if 8 * len(data) + 31 > nbits:
+        raise ValueError("key too short for the input")
+    k = int.from_bytes(key, "big")
+    h = 0
+    for s in range(8 * len(data)):
+        if data[s >> 3] & (0x80 >> (s & 7)):
+            h ^= (k >> (nbits - 32 - s)) & 0xFFFFFFFF
+    return h
+
+
+def flow_key(frame: Optional[bytes], rec, length: int, option: FlowOption = FlowOption()):
+    """(kind, proto, swapped, key bytes) of one frame; kind FLOW_NONE with empty
+    key bytes for a frame without a flow. `rec` is the frame's nexg_record (a
+    numpy record or a dict), `frame` its bytes (None when the extent is not
+    inside the batch's data), `length` len(i) as the frame table gives it."""
+    fl = option.raw_flags()
+    flags = int(rec["flags"])
+    none = (abi.FLOW_NONE, 0, 0, b"")
+    if (flags >> abi.STATUS_SHIFT) & 7:
+        return none
+    if flags & abi.L_IPV4:
+        v6 = False
+        src, dst = int(rec["ip_src"]).to_bytes(4, "big"), int(rec["ip_dst"]).to_bytes(4, "big")
+    elif flags & abi.L_IPV6:
+        l3 = int(rec["l3_off"])
+        if frame is None or length > 65535 or l3 + 40 > length:
+            return none
+        v6 = True
+        src, dst = bytes(frame[l3 + 8: l3 + 24]), bytes(frame[l3 + 24: l3 + 40])
+    else:
+        return none
+    l4 = bool(flags & (abi.L_TCP | abi.L_UDP)) and not fl & abi.FLOW_NO_PORTS
+    if not v6 and int(rec["ip_word"]) & 0x3FFF:  # MF or a fragment offset: NICs hash fragments on the addresses
+        l4 = False
+    sp = int(rec["src_port"]).to_bytes(2, "big") if l4 else b""
+    dp = int(rec["dst_port"]).to_bytes(2, "big") if l4 else b""
+    swapped = 0
+    if fl & abi.FLOW_SYMMETRIC and src + sp > dst + dp:
+        src, dst, sp, dp, swapped = dst, src, dp, sp, 1
+    kind = (abi.FLOW_IPV6 if v6 else abi.FLOW_IPV4) + (1 if l4 else 0)
+    return kind, int(rec["ip_proto"]), swapped, src + dst + sp + dp
+
+
+def flow_host(frame: Optional[bytes], record, length: int, option: FlowOption = FlowOption()) -> Tuple[int, int, int, int]:
+    """nexg_flow_batch's row for one frame: (hash, kind, proto, swapped)."""
+    kind, proto, swapped, key = flow_key(frame, record, length, option)
+    if kind == abi.FLOW_NONE:
+        return 0, abi.FLOW_NONE, 0, 0
+    return toeplitz(key, option.the_key()), kind, proto, swapped
+
+
+def flows_host(frames: Sequence[Optional[bytes]], records, lengths: Sequence[int], option: FlowOption = FlowOption()):
+    """flow_host over a batch as an abi.FLOW_DTYPE array."""
+    out = np.zeros(len(frames), abi.FLOW_DTYPE)
+    for i, fr in enumerate(frames):
+        out[i] = flow_host(fr, records[i], int(lengths[i]), option) + (0,)
+    return out
+
+
+def partition_host(hashes, buckets: int):
+    """nexg_flow_partition on the host: (index u32 [count], bucket_first i64
+    [buckets + 1]) with bucket(i) = hashes[i] % buckets, the index ordered by
+    bucket, then by frame number."""
+    if not 1 <= buckets <= 256:
+        raise ValueError("buckets must be 1..256")
+    b = np.asarray(hashes, np.uint32).astype(np.int64) % buckets
+    index = np.argsort(b, kind="stable").astype(np.uint32)
+    first = np.zeros(buckets + 1, np.int64)
+    first[1:] = np.cumsum(np.bincount(b, minlength=buckets))
+    return index, first
