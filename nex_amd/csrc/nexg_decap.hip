@@ -5,8 +5,9 @@
 // gre.rs:32-107 on Frame.payload), and the order-preserving compaction of the
 // result by inner class. No frame byte is copied: the outputs are offset +
 // length tables over the outer batch's data that nexg_parse_batch takes as
-// they stand.
-#include "parse_kernels.hpp"
+// they stand. Record fields, the header bytes as big-endian words and the
+// compaction's count / rank / scan come from table_kernels.hpp.
+#include "table_kernels.hpp"
 
 namespace nexg {
 
@@ -15,8 +16,7 @@ static_assert(sizeof(nexg_decap_option) == 8, "nexg_decap_option is 8 bytes (inc
 
 // k_decap: one lane per frame. Per lane 48 B of its record (the three 16-B
 // quarters that hold flags / payload_off / payload_len, ip_proto, dst_port),
-// up to 16 tunnel-header bytes as aligned dwords funnel-shifted into place,
-// and one 16-B + one 8-B + one 4-B non-temporal store; consecutive lanes write
+// up to 16 tunnel-header bytes as big-endian words (frame_be_words), and one 16-B + one 8-B + one 4-B non-temporal store; consecutive lanes write
 // consecutive addresses. The candidate test and the GRE flag walk are integer
 // selects: the reference's sequential "remaining < 4" checks (gre.rs:57-77)
 // fail exactly when the payload is shorter than the closed-form header length.
@@ -25,30 +25,26 @@ __global__ __launch_bounds__(256) void k_decap(ParseArgs a, const nexg_record* r
     typedef uint32_t v2u __attribute__((ext_vector_type(2)));
     const uint64_t idx = (uint64_t)blockIdx.x * kTile + threadIdx.x;
     if (idx >= a.count) return;
-    const uint8_t* rp = reinterpret_cast<const uint8_t*>(recs + idx);
-    const uint4 q0 = load16<true>(rp), q1 = load16<true>(rp + 16), q2 = load16<true>(rp + 32);
+    const RecQuarter<0> q0 = rec_quarter<0>(recs + idx);
+    const RecQuarter<1> q1 = rec_quarter<1>(recs + idx);
+    const RecQuarter<2> q2 = rec_quarter<2>(recs + idx);
     uint64_t off;
     uint32_t len;
     const bool ext = frame_extent(a, idx, off, len);
-    const uint32_t flags = q0.x, poff = q0.y & 0xFFFFu, plen = q0.y >> 16;
-    const uint32_t ip_proto = (q1.z >> 8) & 0xFFu, dst_port = q2.w >> 16;
+    const uint32_t flags = rec_dw<kRecFlags>(q0), ip_proto = rec_proto(rec_dw<kRecProto>(q1)),
+                   dst_port = rec_dport(rec_dw<kRecPorts>(q2));
+    uint32_t poff, plen;
+    rec_payload(rec_dw<kRecPayload>(q0), poff, plen);
     // the record is caller memory: clamp to the frame's own extent before any load
-    const bool ok = ext && ((flags >> NEXG_STATUS_SHIFT) & 7u) == 0u && poff + plen <= len;
+    const bool ok = ext && rec_status(flags) == 0u && poff + plen <= len;
     const bool vx = ok && (which & NEXG_DECAP_VXLAN) && (flags & NEXG_L_UDP) && dst_port == vxlan_port;
     const bool gre = ok && !vx && (which & NEXG_DECAP_GRE) && (flags & (NEXG_L_IPV4 | NEXG_L_IPV6)) &&
                      !(flags & (NEXG_L_TRANSPORT | NEXG_L_ICMP | NEXG_L_ICMPV6)) && ip_proto == 47u;
     // header bytes wanted: VXLAN its 8, GRE up to 16 of the payload (the flag
     // bits that size it are in the first dword: no second, dependent load)
     const uint32_t need = vx ? (plen >= 8u ? 8u : 0u) : gre ? (plen >= 4u ? (plen < 16u ? plen : 16u) : 0u) : 0u;
-    const uint64_t A = reinterpret_cast<uint64_t>(a.data) + off + poff;
-    const uint32_t sh = (uint32_t)A & 3u, span = need ? sh + need : 0u;  // bytes from the first aligned dword
-    const auto* dw = NEXG_GLOBAL(uint32_t, reinterpret_cast<const void*>(A & ~3ull));
-    uint32_t d[5];
-#pragma unroll
-    for (uint32_t k = 0; k < 5; k++) d[k] = 4u * k < span ? dw[k] : 0u;  // every dword loaded holds a wanted byte
     uint32_t w[4];  // header bytes 4j..4j+3 as big-endian values
-#pragma unroll
-    for (uint32_t j = 0; j < 4; j++) w[j] = __builtin_bswap32(__builtin_amdgcn_alignbyte(d[j + 1], d[j], sh));
+    frame_be_words(reinterpret_cast<uint64_t>(a.data) + off + poff, need != 0u, need, w);
 
     // VXLAN (vxlan.rs:34-50): flags u8, reserved1 u24, vni u24, reserved2 u8
     // GRE (gre.rs:38-77): flags u16, protocol_type u16, then checksum + offset
@@ -86,8 +82,9 @@ hipError_t launch_decap(const ParseArgs& a, const nexg_record* recs, uint32_t wh
     return hipGetLastError();
 }
 
-// ---- nexg_decap_select: count per 256-frame tile, scan of the tile counts,
-// scatter. Positions come from ballots, mbcnt ranks and scans alone.
+// ---- nexg_decap_select: count per 256-frame tile (block_count), scan of the
+// tile counts (k_tile_scan), scatter by rank. Positions come from ballots,
+// mbcnt ranks and scans alone.
 
 // first dword of a nexg_tunnel: kind | status << 8 | inner << 16 | hdr_len << 24
 __device__ __forceinline__ bool decap_selected(const nexg_tunnel* tunnels, uint64_t idx, uint64_t count,
@@ -102,37 +99,8 @@ __global__ __launch_bounds__(256) void k_decap_count(const nexg_tunnel* tunnels,
                                                      uint32_t* tile_count) {
     __shared__ uint32_t s_w[4];
     const uint64_t idx = (uint64_t)blockIdx.x * kTile + threadIdx.x;
-    const uint64_t m = __ballot(decap_selected(tunnels, idx, count, inner_mask));
-    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = (uint32_t)__builtin_popcountll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) tile_count[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-}
-
-// one workgroup: the tile counts become their exclusive scan in place, 256
-// tiles per step (a wave scan, the four wave totals through LDS, a running
-// carry); one lane stores the total
-__global__ __launch_bounds__(256) void k_decap_scan(uint32_t* tile_count, uint64_t tiles, uint64_t* out_count) {
-    __shared__ uint32_t s_w[4];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
-    uint64_t carry = 0;
-    for (uint64_t c = 0; c < tiles; c += kTile) {
-        const uint32_t v = c + t < tiles ? tile_count[c + t] : 0u;
-        uint32_t x = v;  // inclusive scan within the wave
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d, 64);
-            if (lane >= (uint32_t)d) x += y;
-        }
-        if (lane == 63u) s_w[wv] = x;
-        __syncthreads();
-        uint32_t below = 0;
-        for (uint32_t k = 0; k < wv; k++) below += s_w[k];
-        const uint32_t total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        if (c + t < tiles) tile_count[c + t] = (uint32_t)carry + below + x - v;
-        carry += total;
-        __syncthreads();  // s_w is rewritten by the next step
-    }
-    if (t == 0) *out_count = carry;
+    const uint32_t total = block_count(decap_selected(tunnels, idx, count, inner_mask), s_w).total;
+    if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(256) void k_decap_scatter(const nexg_tunnel* tunnels, const uint64_t* inner_off,
@@ -142,16 +110,12 @@ __global__ __launch_bounds__(256) void k_decap_scatter(const nexg_tunnel* tunnel
     __shared__ uint32_t s_w[4];
     const uint64_t idx = (uint64_t)blockIdx.x * kTile + threadIdx.x;
     const bool sel = decap_selected(tunnels, idx, count, inner_mask);
-    const uint64_t m = __ballot(sel);
-    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = (uint32_t)__builtin_popcountll(m);
-    __syncthreads();
+    const uint32_t rank = block_count(sel, s_w).rank;
     if (!sel) return;
-    uint32_t below = 0;
-    for (uint32_t w = 0; w < (threadIdx.x >> 6); w++) below += s_w[w];
     // rank < the number selected <= count: inside the outputs' capacity (checked
     // all the same: a caller rewriting `tunnels` between the passes must not
     // turn into a store out of bounds)
-    const uint64_t k = (uint64_t)tile_base[blockIdx.x] + below + lanes_below(m);
+    const uint64_t k = (uint64_t)tile_base[blockIdx.x] + rank;
     if (k >= count) return;
     out_index[k] = (uint32_t)idx;
     out_off[k] = NEXG_GLOBAL(uint64_t, inner_off)[idx];
@@ -165,7 +129,7 @@ hipError_t launch_decap_select(const nexg_tunnel* tunnels, const uint64_t* inner
     if (tiles)
         hipLaunchKernelGGL(k_decap_count, dim3((uint32_t)tiles), dim3(kTile), 0, s, tunnels, count, inner_mask,
                            tile_count);
-    hipLaunchKernelGGL(k_decap_scan, dim3(1), dim3(kTile), 0, s, tile_count, tiles, out_count);
+    hipLaunchKernelGGL(k_tile_scan<uint32_t>, dim3(1), dim3(kTile), 0, s, tile_count, tiles, out_count);
     if (tiles)
         hipLaunchKernelGGL(k_decap_scatter, dim3((uint32_t)tiles), dim3(kTile), 0, s, tunnels, inner_off, inner_len,
                            count, inner_mask, tile_count, out_index, out_off, out_len);

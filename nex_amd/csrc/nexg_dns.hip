@@ -7,8 +7,9 @@
 // table in two levels: per frame within its 256-frame tile, per tile within
 // the batch); nexg_dns_entries walks again and stores one 16-B entry per query
 // / resource record at the position the sums give. Positions come from scans
-// alone: no atomics, the same output on every run.
-#include "parse_kernels.hpp"
+// alone (block_excl_scan and k_tile_scan of table_kernels.hpp): no atomics, the
+// same output on every run.
+#include "table_kernels.hpp"
 
 namespace nexg {
 
@@ -103,10 +104,9 @@ __device__ __forceinline__ DnsWalk dns_walk(const uint8_t* m, uint32_t n, uint32
 // k_dns_walk: one lane per frame, 256-frame workgroups. Per lane the two 16-B
 // quarters of its record that hold flags / payload_off / payload_len and the
 // ports, the walk's dependent byte loads, then the workgroup's exclusive scan
-// of the per-lane entry counts (a wave scan, the four wave totals through
-// LDS) and the 32-B summary as two adjacent 16-B non-temporal stores:
-// consecutive lanes write consecutive addresses. Lanes past the batch take
-// part in the scan with count 0 (no early return before the barrier).
+// of the per-lane entry counts (block_excl_scan: lanes past the batch take part
+// with count 0) and the 32-B summary as two adjacent 16-B non-temporal stores:
+// consecutive lanes write consecutive addresses.
 __global__ __launch_bounds__(256) void k_dns_walk(ParseArgs a, const nexg_record* recs, uint32_t any_udp, uint32_t port,
                                                   nexg_dns* out, uint64_t* tile_first) {
     __shared__ uint32_t s_w[4];
@@ -115,16 +115,16 @@ __global__ __launch_bounds__(256) void k_dns_walk(ParseArgs a, const nexg_record
     uint32_t status = 0, f8 = 0, poff = 0, plen = 0, id = 0, hflags = 0, qd = 0, an = 0, ns = 0, ar = 0;
     DnsWalk w{0u, 0u, 0u, 0u, 0u, false};
     if (valid) {
-        const uint8_t* rp = reinterpret_cast<const uint8_t*>(recs + idx);
-        const uint4 q0 = load16<true>(rp), q2 = load16<true>(rp + 32);
+        const RecQuarter<0> q0 = rec_quarter<0>(recs + idx);
+        const RecQuarter<2> q2 = rec_quarter<2>(recs + idx);
         uint64_t off;
         uint32_t len;
         const bool ext = frame_extent(a, idx, off, len);
-        const uint32_t flags = q0.x, sport = q2.w & 0xFFFFu, dport = q2.w >> 16;
-        poff = q0.y & 0xFFFFu;
-        plen = q0.y >> 16;
+        const uint32_t flags = rec_dw<kRecFlags>(q0), ports = rec_dw<kRecPorts>(q2);
+        const uint32_t sport = rec_sport(ports), dport = rec_dport(ports);
+        rec_payload(rec_dw<kRecPayload>(q0), poff, plen);
         // the record is caller memory: clamp to the frame's own extent before any load
-        const bool cand = ext && ((flags >> NEXG_STATUS_SHIFT) & 7u) == 0u && (flags & NEXG_L_UDP) && plen > 0u &&
+        const bool cand = ext && rec_status(flags) == 0u && (flags & NEXG_L_UDP) && plen > 0u &&
                           poff + plen <= len && (any_udp || sport == port || dport == port);
         if (!cand) {
             poff = plen = 0u;
@@ -146,50 +146,14 @@ __global__ __launch_bounds__(256) void k_dns_walk(ParseArgs a, const nexg_record
         }
     }
     const uint32_t v = w.n_q + w.n_an + w.n_ns + w.n_ar;  // <= 65535 / 5 per lane: a tile's total fits 32 bits
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    uint32_t x = v;  // inclusive scan within the wave
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
-        if (lane >= (uint32_t)d) x += y;
-    }
-    if (lane == 63u) s_w[wv] = x;
-    __syncthreads();
-    uint32_t below = 0;
-    for (uint32_t k = 0; k < wv; k++) below += s_w[k];
-    if (threadIdx.x == 0) tile_first[blockIdx.x] = (uint64_t)s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    uint32_t total;
+    const uint32_t first = block_excl_scan(v, s_w, total);
+    if (threadIdx.x == 0) tile_first[blockIdx.x] = total;
     if (!valid) return;
     const u32x4 lo{status | (f8 << 8) | (poff << 16), plen | (id << 16), hflags | (qd << 16), an | (ns << 16)};
-    const u32x4 hi{ar | (w.n_q << 16), w.n_an | (w.n_ns << 16), w.n_ar | (w.pos << 16), below + x - v};
+    const u32x4 hi{ar | (w.n_q << 16), w.n_an | (w.n_ns << 16), w.n_ar | (w.pos << 16), first};
     __builtin_nontemporal_store(lo, reinterpret_cast<u32x4*>(out) + idx * 2u);
     __builtin_nontemporal_store(hi, reinterpret_cast<u32x4*>(out) + idx * 2u + 1u);
-}
-
-// one workgroup: the tile totals become their exclusive scan in place, 256
-// tiles per step (a wave scan, the four wave totals through LDS, a running
-// carry); one lane stores the batch total behind them
-__global__ __launch_bounds__(256) void k_dns_scan(uint64_t* tile_first, uint64_t tiles) {
-    __shared__ uint64_t s_w[4];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
-    uint64_t carry = 0;
-    for (uint64_t c = 0; c < tiles; c += kTile) {
-        const uint64_t v = c + t < tiles ? tile_first[c + t] : 0ull;
-        uint64_t x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint64_t y = __shfl_up((unsigned long long)x, d, 64);
-            if (lane >= (uint32_t)d) x += y;
-        }
-        if (lane == 63u) s_w[wv] = x;
-        __syncthreads();
-        uint64_t below = 0;
-        for (uint32_t k = 0; k < wv; k++) below += s_w[k];
-        const uint64_t total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        if (c + t < tiles) tile_first[c + t] = carry + below + x - v;
-        carry += total;
-        __syncthreads();  // s_w is rewritten by the next step
-    }
-    if (t == 0) tile_first[tiles] = carry;
 }
 
 // k_dns_fill: one lane per frame; the same walk with the stores switched on.
@@ -222,7 +186,8 @@ hipError_t launch_dns(const ParseArgs& a, const nexg_record* recs, uint32_t any_
     if (tiles)
         hipLaunchKernelGGL(k_dns_walk, dim3((uint32_t)tiles), dim3(kTile), 0, s, a, recs, any_udp, port, out,
                            tile_first);
-    hipLaunchKernelGGL(k_dns_scan, dim3(1), dim3(kTile), 0, s, tile_first, tiles);
+    // the tile totals become their exclusive scan in place, the batch total behind them (tiles == 0: tile_first[0] = 0)
+    hipLaunchKernelGGL(k_tile_scan<uint64_t>, dim3(1), dim3(kTile), 0, s, tile_first, tiles, tile_first + tiles);
     return hipGetLastError();
 }
 

@@ -27,9 +27,8 @@ constexpr uint32_t kFlowNibbles = 72;  // 36 key bytes at most
 // collide, and the bit-serial form costs three VALU steps per key bit (864 for
 // an IPv6 frame with ports against 72 lookups). Per lane: 48 B of its record
 // (the three 16-B quarters that hold flags / l3_off, ip_word / ip_proto /
-// ip_src, ip_dst / the ports), for an IPv6 frame its two addresses as aligned
-// dwords byte-aligned in registers (every dword loaded holds an address byte:
-// the loads stay inside the frame's own 16-B blocks), and one 8-B
+// ip_src, ip_dst / the ports), for an IPv6 frame its two addresses as
+// big-endian words (frame_be_words of table_kernels.hpp), and one 8-B
 // non-temporal store; consecutive lanes write consecutive rows. Words no lane
 // of the wave has (the IPv6 words in a wave of IPv4 frames) are skipped by
 // wave-uniform branches; a lane with a shorter key looks up nibble 0 there,
@@ -56,34 +55,29 @@ __global__ __launch_bounds__(256) void k_flow(ParseArgs a, const nexg_record* re
     __syncthreads();
     const uint64_t idx = (uint64_t)blockIdx.x * kTile + t;
     if (idx >= a.count) return;
-    const uint8_t* rp = reinterpret_cast<const uint8_t*>(recs + idx);
-    const uint4 q0 = load16<true>(rp), q1 = load16<true>(rp + 16), q2 = load16<true>(rp + 32);
+    const RecQuarter<0> q0 = rec_quarter<0>(recs + idx);
+    const RecQuarter<1> q1 = rec_quarter<1>(recs + idx);
+    const RecQuarter<2> q2 = rec_quarter<2>(recs + idx);
     uint64_t off, l64;
     const bool ext = table_extent(a, idx, off, l64);
-    const uint32_t flags = q0.x, l3 = q0.w & 0xFFFFu, ip_word = q1.y, proto = (q1.z >> 8) & 0xFFu;
-    const bool ok = ((flags >> NEXG_STATUS_SHIFT) & 7u) == 0u;
+    const uint32_t flags = rec_dw<kRecFlags>(q0), l3 = rec_l3(rec_dw<kRecL3>(q0)), ip_word = rec_dw<kRecIpWord>(q1),
+                   proto = rec_proto(rec_dw<kRecProto>(q1)), ports_dw = rec_dw<kRecPorts>(q2);
+    const bool ok = rec_status(flags) == 0u;
     const bool v4 = ok && (flags & NEXG_L_IPV4) != 0u;
     // the record is caller memory: the header must lie inside the frame's own extent before any load
     const bool v6 = ok && !v4 && (flags & NEXG_L_IPV6) != 0u && ext && (uint64_t)l3 + 40u <= l64;
     const bool has = v4 || v6;
     const bool l4 = has && (flags & (NEXG_L_TCP | NEXG_L_UDP)) != 0u && !(opt & NEXG_FLOW_NO_PORTS) &&
                     !(v4 && (ip_word & 0x3FFFu) != 0u);
-    uint32_t S[4] = {v4 ? q1.w : 0u, 0u, 0u, 0u}, D[4] = {v4 ? q2.x : 0u, 0u, 0u, 0u};
+    uint32_t S[4] = {v4 ? rec_dw<kRecSrc>(q1) : 0u, 0u, 0u, 0u}, D[4] = {v4 ? rec_dw<kRecDst>(q2) : 0u, 0u, 0u, 0u};
     if (__ballot(v6) != 0ull) {
-        const uint64_t A = reinterpret_cast<uint64_t>(a.data) + off + l3 + 8u;
-        const uint32_t sh = (uint32_t)A & 3u;
-        const auto* dw = NEXG_GLOBAL(uint32_t, reinterpret_cast<const void*>(A & ~3ull));
-        uint32_t d[9];
+        uint32_t a6[8];  // the source, then the destination
+        frame_be_words(reinterpret_cast<uint64_t>(a.data) + off + l3 + 8u, v6, 32u, a6);
 #pragma unroll
-        for (uint32_t k = 0; k < 9; k++) d[k] = v6 && 4u * k < sh + 32u ? dw[k] : 0u;  // every dword holds an address byte
-#pragma unroll
-        for (uint32_t j = 0; j < 4; j++) {
-            const uint32_t s = __builtin_bswap32(__builtin_amdgcn_alignbyte(d[j + 1], d[j], sh));
-            const uint32_t e = __builtin_bswap32(__builtin_amdgcn_alignbyte(d[j + 5], d[j + 4], sh));
-            if (v6) S[j] = s, D[j] = e;
-        }
+        for (uint32_t j = 0; j < 4; j++)
+            if (v6) S[j] = a6[j], D[j] = a6[j + 4];
     }
-    uint32_t sport = l4 ? q2.w & 0xFFFFu : 0u, dport = l4 ? q2.w >> 16 : 0u;
+    uint32_t sport = l4 ? rec_sport(ports_dw) : 0u, dport = l4 ? rec_dport(ports_dw) : 0u;
     // NEXG_FLOW_SYMMETRIC: (source address, src_port) > (destination address, dst_port) as byte strings
     bool gt = sport > dport, decided = false;
 #pragma unroll
@@ -182,8 +176,8 @@ __global__ __launch_bounds__(256) void k_part_count(const nexg_flow* flows, uint
 }
 
 // the hierarchical scan of the n = P * T counters: sums of 1024-counter chunks,
-// k_tile_scan over the chunk sums, then each chunk's own exclusive scan on top
-// of its base. No workgroup waits for another.
+// (block_sum), k_tile_scan over the chunk sums, then each chunk's own exclusive
+// scan (block_excl_scan) on top of its base. No workgroup waits for another.
 __global__ __launch_bounds__(256) void k_chunk_sums(const uint32_t* v, uint64_t n, uint32_t* sums) {
     __shared__ uint32_t s_w[4];
     const uint64_t base = (uint64_t)blockIdx.x * kScanChunk;
@@ -193,34 +187,20 @@ __global__ __launch_bounds__(256) void k_chunk_sums(const uint32_t* v, uint64_t 
         const uint64_t i = base + k * kTile + threadIdx.x;
         if (i < n) x += v[i];
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) sums[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    const uint32_t sum = (uint32_t)block_sum(x, s_w);
+    if (threadIdx.x == 0) sums[blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(256) void k_chunk_apply(uint32_t* v, uint64_t n, const uint32_t* sums) {
     __shared__ uint32_t s_w[4];
-    const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
     const uint64_t base = (uint64_t)blockIdx.x * kScanChunk;
     uint32_t carry = sums[blockIdx.x];
 #pragma unroll
     for (uint32_t k = 0; k < kScanChunk / kTile; k++) {
-        const uint64_t i = base + k * kTile + t;
-        const uint32_t val = i < n ? v[i] : 0u;
-        uint32_t x = val;  // inclusive scan within the wave
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d, 64);
-            if (lane >= (uint32_t)d) x += y;
-        }
-        if (lane == 63u) s_w[wv] = x;
-        __syncthreads();
-        uint32_t below = 0;
-        for (uint32_t j = 0; j < wv; j++) below += s_w[j];
-        const uint32_t total = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        if (i < n) v[i] = carry + below + x - val;
+        const uint64_t i = base + k * kTile + threadIdx.x;
+        uint32_t total;
+        const uint32_t before = block_excl_scan(i < n ? v[i] : 0u, s_w, total);
+        if (i < n) v[i] = carry + before;
         carry += total;
         __syncthreads();  // s_w is rewritten by the next step
     }
@@ -260,16 +240,8 @@ __global__ __launch_bounds__(256) void k_part_scatter(ParseArgs a, const nexg_fl
         uint32_t c[4], tot = 0;
 #pragma unroll
         for (uint32_t k = 0; k < 4; k++) c[k] = s_w[k][t], tot += c[k];  // 0 for t >= P
-        uint32_t x = tot;  // inclusive scan of the bucket totals within the wave
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d, 64);
-            if (lane >= (uint32_t)d) x += y;
-        }
-        if (lane == 63u) s_ws[wv] = x;
-        __syncthreads();
-        uint32_t run = x - tot;  // the bucket's first position in the tile's order
-        for (uint32_t j = 0; j < wv; j++) run += s_ws[j];
+        uint32_t frames;
+        uint32_t run = block_excl_scan(tot, s_ws, frames);  // the bucket's first position in the tile's order
         const uint32_t b0 = t < P ? base[(uint64_t)t * T + blockIdx.x] : 0u;
         s_delta[t] = b0 - run;
 #pragma unroll

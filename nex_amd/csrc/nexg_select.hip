@@ -3,8 +3,9 @@
 // batch already parsed with NEXG_OUT_RECORD that tests each frame's record
 // against up to 16 rules and compacts the matching frames' table entries in
 // order (count per 256-frame tile, scan of the tile counts, scatter: the shape
-// of nexg_decap_select), then the gather that copies the selected frames into
-// one dense buffer and compacts per-frame rows by the selected index.
+// of nexg_decap_select, on the same primitives of table_kernels.hpp), then the
+// gather that copies the selected frames into one dense buffer and compacts
+// per-frame rows by the selected index.
 #include "table_kernels.hpp"
 
 namespace nexg {
@@ -93,42 +94,32 @@ __device__ __forceinline__ bool prefix4(const uint32_t* a, const uint32_t* w, co
 // One lane's verdict: the lowest matching rule, or NEXG_RULE_NONE. The filter is
 // a kernel argument and the rule loop is wave-uniform, so the rules stay in
 // scalar registers. Only the record dwords some rule tests are loaded (f.need),
-// and frame bytes (the two IPv6 addresses, as aligned dwords byte-aligned in
-// registers) only under a family-6 rule, only by lanes whose header is whole
-// inside their own frame.
+// and frame bytes (the two IPv6 addresses, by frame_be_words) only under a
+// family-6 rule, only by lanes whose header is whole inside their own frame.
 __device__ __forceinline__ uint32_t select_rule(const ParseArgs& a, const nexg_record* recs, const SelFilter& f,
                                                 uint64_t idx, uint64_t& off, uint32_t& len32) {
     uint64_t l64;
     const bool ext = table_extent(a, idx, off, l64);
     len32 = l64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)l64;
     const auto* rw = NEXG_GLOBAL(uint32_t, recs) + idx * 16u;
-    const uint32_t flags = rw[0];
-    const bool ok = ((flags >> NEXG_STATUS_SHIFT) & 7u) == 0u;
+    const uint32_t flags = rw[kRecFlags];
+    const bool ok = rec_status(flags) == 0u;
     uint32_t proto = 0, src4 = 0, dst4 = 0, ports = 0, tcpf = 0;
-    if (f.need & kSelNeedProto) proto = (rw[6] >> 8) & 0xFFu;
-    if (f.need & kSelNeedSrc4) src4 = rw[7];
-    if (f.need & kSelNeedDst4) dst4 = rw[8];
-    if (f.need & kSelNeedPorts) ports = rw[11];
-    if (f.need & kSelNeedTcp) tcpf = (rw[12] >> 16) & 0xFFu;
+    if (f.need & kSelNeedProto) proto = rec_proto(rw[kRecProto]);
+    if (f.need & kSelNeedSrc4) src4 = rw[kRecSrc];
+    if (f.need & kSelNeedDst4) dst4 = rw[kRecDst];
+    if (f.need & kSelNeedPorts) ports = rw[kRecPorts];
+    if (f.need & kSelNeedTcp) tcpf = rec_l4_type(rw[kRecL4Type]);
     const bool l4 = ok && (flags & (NEXG_L_TCP | NEXG_L_UDP)) != 0u;
     const bool v4 = ok && (flags & NEXG_L_IPV4) != 0u;
     bool v6 = false;
-    uint32_t s6[4] = {0, 0, 0, 0}, d6[4] = {0, 0, 0, 0};
+    uint32_t a6[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // the IPv6 source, then the destination
     if (f.need & kSelNeedV6) {
-        const uint32_t l3 = rw[3] & 0xFFFFu;
+        const uint32_t l3 = rec_l3(rw[kRecL3]);
         v6 = ok && ext && (flags & NEXG_L_IPV6) != 0u && (uint64_t)l3 + 40u <= l64;
-        const uint64_t A = reinterpret_cast<uint64_t>(a.data) + off + l3 + 8u;
-        const uint32_t sh = (uint32_t)A & 3u;
-        const auto* dw = NEXG_GLOBAL(uint32_t, reinterpret_cast<const void*>(A & ~3ull));
-        uint32_t d[9];
-#pragma unroll
-        for (uint32_t k = 0; k < 9; k++) d[k] = v6 && 4u * k < sh + 32u ? dw[k] : 0u;  // every dword holds an address byte
-#pragma unroll
-        for (uint32_t j = 0; j < 4; j++) {
-            s6[j] = __builtin_bswap32(__builtin_amdgcn_alignbyte(d[j + 1], d[j], sh));
-            d6[j] = __builtin_bswap32(__builtin_amdgcn_alignbyte(d[j + 5], d[j + 4], sh));
-        }
+        frame_be_words(reinterpret_cast<uint64_t>(a.data) + off + l3 + 8u, v6, 32u, a6);
     }
+    const uint32_t *s6 = a6, *d6 = a6 + 4;
     const uint32_t s4[4] = {src4, 0, 0, 0}, d4[4] = {dst4, 0, 0, 0};
     uint32_t hit = NEXG_RULE_NONE;
     for (uint32_t r = 0; r < f.n_rules; r++) {
@@ -136,9 +127,9 @@ __device__ __forceinline__ uint32_t select_rule(const ParseArgs& a, const nexg_r
         const uint32_t t = R.tests, fam = R.misc >> 24;
         bool m = (flags & R.flags_mask) == R.flags_value;
         if (t & NEXG_RULE_PROTO) m = m && ok && (flags & (NEXG_L_IPV4 | NEXG_L_IPV6)) != 0u && proto == (R.misc & 0xFFu);
-        if (t & NEXG_RULE_SRC_PORT) m = m && l4 && in_range(ports & 0xFFFFu, R.sport);
-        if (t & NEXG_RULE_DST_PORT) m = m && l4 && in_range(ports >> 16, R.dport);
-        if (t & NEXG_RULE_ANY_PORT) m = m && l4 && (in_range(ports & 0xFFFFu, R.sport) || in_range(ports >> 16, R.sport));
+        if (t & NEXG_RULE_SRC_PORT) m = m && l4 && in_range(rec_sport(ports), R.sport);
+        if (t & NEXG_RULE_DST_PORT) m = m && l4 && in_range(rec_dport(ports), R.dport);
+        if (t & NEXG_RULE_ANY_PORT) m = m && l4 && (in_range(rec_sport(ports), R.sport) || in_range(rec_dport(ports), R.sport));
         if (t & (NEXG_RULE_SRC_ADDR | NEXG_RULE_DST_ADDR | NEXG_RULE_ANY_ADDR)) {
             const bool six = fam == 6u;
             m = m && (six ? v6 : v4);
@@ -171,10 +162,8 @@ __global__ __launch_bounds__(256) void k_select_count(SelArgs p, uint32_t* tile_
         uint32_t len;
         sel = (select_rule(p.a, p.recs, p.f, idx, off, len) != NEXG_RULE_NONE) != (p.f.invert != 0u);
     }
-    const uint64_t m = __ballot(sel);
-    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = (uint32_t)__builtin_popcountll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) tile_count[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    const uint32_t total = block_count(sel, s_w).total;
+    if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(256) void k_select_scatter(SelArgs p, const uint32_t* tile_base, uint32_t* out_index,
@@ -188,16 +177,12 @@ __global__ __launch_bounds__(256) void k_select_scatter(SelArgs p, const uint32_
         hit = select_rule(p.a, p.recs, p.f, idx, off, len);
         sel = (hit != NEXG_RULE_NONE) != (p.f.invert != 0u);
     }
-    const uint64_t m = __ballot(sel);
-    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = (uint32_t)__builtin_popcountll(m);
-    __syncthreads();
+    const uint32_t rank = block_count(sel, s_w).rank;
     if (!sel) return;
-    uint32_t below = 0;
-    for (uint32_t w = 0; w < (threadIdx.x >> 6); w++) below += s_w[w];
     // rank < the number selected <= count: inside the outputs' capacity (checked
     // all the same: a caller rewriting the records or the workspace between
     // the passes must not turn into a store out of bounds)
-    const uint64_t k = (uint64_t)tile_base[blockIdx.x] + below + lanes_below(m);
+    const uint64_t k = (uint64_t)tile_base[blockIdx.x] + rank;
     if (k >= p.a.count) return;
     out_index[k] = (uint32_t)idx;
     out_off[k] = off;
@@ -232,33 +217,18 @@ __device__ __forceinline__ uint32_t plan_padded(const ParseArgs& a, uint64_t idx
 __global__ __launch_bounds__(256) void k_plan_sum(ParseArgs a, uint32_t align, uint64_t* tile_sum) {
     __shared__ uint32_t s_w[4];
     uint32_t copied;
-    uint32_t x = plan_padded(a, (uint64_t)blockIdx.x * kTile + threadIdx.x, align, copied);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = (uint64_t)s_w[0] + s_w[1] + s_w[2] + s_w[3];  // < 2^24 + pads
+    const uint64_t sum = block_sum(plan_padded(a, (uint64_t)blockIdx.x * kTile + threadIdx.x, align, copied), s_w);
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = sum;  // < 2^24 + pads
 }
 
 __global__ __launch_bounds__(256) void k_plan_write(ParseArgs a, uint32_t align, const uint64_t* tile_base,
                                                     uint64_t* out_offsets, uint32_t* out_len) {
     __shared__ uint32_t s_w[4];
     const uint64_t idx = (uint64_t)blockIdx.x * kTile + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    uint32_t copied;
-    const uint32_t v = plan_padded(a, idx, align, copied);
-    uint32_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
-        if (lane >= (uint32_t)d) x += y;
-    }
-    if (lane == 63u) s_w[wv] = x;
-    __syncthreads();
+    uint32_t copied, total;
+    const uint32_t before = block_excl_scan(plan_padded(a, idx, align, copied), s_w, total);
     if (idx >= a.count) return;
-    uint32_t below = 0;
-    for (uint32_t k = 0; k < wv; k++) below += s_w[k];
-    out_offsets[idx] = tile_base[blockIdx.x] + below + x - v;
+    out_offsets[idx] = tile_base[blockIdx.x] + before;
     if (out_len) out_len[idx] = copied;
 }
 

@@ -45,6 +45,17 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
     return v;
 }
 
+// the 64-bit form, for the second passes' scans (table_kernels.hpp)
+__device__ __forceinline__ uint64_t wave_incl_scan(uint64_t v) {
+    const uint32_t lane = threadIdx.x & 63u;
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint64_t u = __shfl_up((unsigned long long)v, d, 64);
+        if (lane >= d) v += u;
+    }
+    return v;
+}
+
 constexpr uint32_t kPiece = 256;  // bytes per piece = 16 lanes x 16 B
 
 template <int OUT>
