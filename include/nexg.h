@@ -878,7 +878,8 @@ int nexg_gather_rows(nexg_ctx* ctx, const void* rows, uint32_t row_bytes, uint64
 /* ---- flow keys, RSS hash and flow-affine partition (extension) -----------------
  * The reference has no flow notion; like the selection above this is an
  * extension, and the text below is its whole specification
- * (nex_amd/flow.py flow_host / partition_host restate it on the host).
+ * (nex_amd/flow.py flow_host / partition_host / sort_host / groups_host
+ * restate it on the host).
  * nexg_flow_batch gives every frame of a batch already parsed with
  * NEXG_OUT_RECORD (any parse option; an inner table from nexg_decap_batch with
  * its inner records works too) an 8-byte flow row: the Toeplitz RSS hash of its
@@ -989,6 +990,89 @@ static inline uint64_t nexg_flow_partition_workspace(uint64_t count, uint32_t bu
     const uint64_t counters = tiles * buckets;
     const uint64_t chunks = (counters + 1023u) / 1024u;
     return 8u + 4u * ((chunks + 1u) & ~(uint64_t)1u) + 4u * counters;
+}
+
+/* Per-flow counters: sort a batch by flow hash, then reduce it to one row per
+ * run of equal hashes.
+ *
+ * nexg_flow_sort: out_index[k] (count entries, 4-B aligned) = the frame number
+ * of the k-th frame when the frames are ordered by (flows[i].hash ascending,
+ * i ascending). All frames take part; frames without a flow have hash 0 and
+ * come first. It is a stable LSD radix sort: four 8-bit digit passes over
+ * (hash, index) pairs held in the workspace, each pass the partition's count
+ * kernel, three-kernel counter scan and scatter at 256 buckets; the first pass
+ * makes the pairs from `flows`, the last stores the frame numbers alone.
+ * Positions come from ballots, ranks and scans only (no atomics): a run
+ * repeats bit for bit. `flows` and the workspace are caller memory: every
+ * store is bounded by `count`, whatever they hold between the passes.
+ * workspace: device memory (8-B aligned) of at least the sort's workspace
+ * helper's bytes. count == 0 launches nothing. NEXG_EINVAL: count > 2^32 - 1,
+ * a NULL or misaligned pointer (flows 8 B, out_index 4 B, workspace 8 B), a
+ * short workspace. Twenty kernels on `stream`. */
+int nexg_flow_sort(nexg_ctx* ctx, const nexg_flow* flows, uint64_t count, uint32_t* out_index, void* workspace,
+                   uint64_t workspace_bytes, void* stream);
+/* the partition's workspace at 256 buckets, then two buffers of `count`
+ * 8-byte pairs */
+static inline uint64_t nexg_flow_sort_workspace(uint64_t count) {
+    return nexg_flow_partition_workspace(count, 256u) + 16u * count;
+}
+
+/* nexg_flow_groups: a group is a maximal run of equal flows[order[k]].hash in
+ * `order` (nexg_flow_sort's out_index); groups are numbered in run order, so
+ * ascending by hash. *out_count (device memory, 8-B aligned) = the number of
+ * groups, written even when it exceeds groups_cap; rows at or past groups_cap
+ * are not stored. out_group (optional, count entries, 4-B aligned):
+ * out_group[order[k]] = the group number of position k, defined when `order`
+ * is a permutation.
+ *
+ * The key of a frame is (kind, proto, key bytes), recomputed from its record
+ * and frame bytes exactly as nexg_flow_batch documents above under `option`'s
+ * NEXG_FLOW_SYMMETRIC / NEXG_FLOW_NO_PORTS (which frames have a flow, the IPv4
+ * fragment rule, the IPv6 addresses from [l3_off + 8, l3_off + 40), the
+ * exchange of the endpoints); the Toeplitz key plays no part. Two frames
+ * without a flow have equal keys. `mixed` counts the positions k of the group
+ * other than its first whose key differs from the key of position k - 1:
+ * mixed == 0 if and only if the group is exactly one flow, and a nonzero
+ * `mixed` marks a 32-bit hash collision, which the caller resolves from the
+ * members order[first .. first + packets).
+ *
+ * `order`, `flows`, `records` and the workspace are caller memory. An order
+ * entry >= count stands for a frame with an all-zero flow row, no key and
+ * length 0: nothing is read for it and it gets no out_group store. Nothing
+ * outside a frame's own 16-B blocks is read, and no store leaves
+ * out[0, groups_cap), out_group[0, count) or *out_count.
+ *
+ * One kernel per sorted position computes a head flag (the hash differs from
+ * the position before), a break flag (same hash, another key) and the length,
+ * and scans them inside its 256-position tile; one-workgroup scans of the
+ * tiles' totals, a kernel that numbers the groups, and one lane per group
+ * taking differences of the prefixes follow. The work is linear in `count`
+ * however the groups are sized; no atomics. count == 0 writes *out_count = 0
+ * and launches nothing else. NEXG_EINVAL: unknown option flag bits,
+ * reserved != 0, a NULL or misaligned pointer (records 16 B, out 16 B, flows /
+ * out_count / workspace 8 B, order / out_group 4 B), an invalid frame table,
+ * count > 2^32 - 1, a short workspace. Six kernels on `stream`. */
+typedef struct nexg_flow_group { /* 32 bytes */
+    uint32_t hash;        /* flows[first_index].hash */
+    uint8_t kind, proto;  /* flows[first_index].kind / .proto */
+    uint8_t flags8;       /* bit 0: mixed != 0 */
+    uint8_t reserved;     /* 0 */
+    uint32_t first;       /* position in `order` of the group's first member */
+    uint32_t packets;     /* members: order[first .. first + packets) */
+    uint64_t bytes;       /* sum of len(i) over the members with a valid extent (else 0) */
+    uint32_t mixed;       /* members whose key differs from the member before them in the group */
+    uint32_t first_index; /* order[first]: the group's earliest frame */
+} nexg_flow_group;
+int nexg_flow_groups(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records, const nexg_flow* flows,
+                     const nexg_flow_option* option /* as given to nexg_flow_batch; NULL = defaults */,
+                     const uint32_t* order, nexg_flow_group* out, uint64_t groups_cap, uint32_t* out_group,
+                     uint64_t* out_count, void* workspace, uint64_t workspace_bytes, void* stream);
+/* 16 B (two scan totals), per 256-position tile a u64 and two u32 (padded to
+ * an even count), per position a u64 of in-tile prefixes and a u32 group start */
+static inline uint64_t nexg_flow_groups_workspace(uint64_t count) {
+    const uint64_t tiles = (count + 255u) / 256u;
+    const uint64_t tp = (tiles + 1u) & ~(uint64_t)1u;
+    return 16u + 8u * tiles + 8u * count + 8u * tp + 4u * ((count + 1u) & ~(uint64_t)1u);
 }
 
 /* ---- calibration (not a reference entry point) ---------------------------

@@ -31,6 +31,9 @@
  *                           no reference counterpart (an extension): the
  *                           Toeplitz RSS hash of every frame's flow key and the
  *                           stable split of a batch into flow-affine buckets
+ *   FlowGroup, Engine::flow_sort / flow_groups / flow_group_bufs
+ *                           per-flow counters (an extension): the batch sorted
+ *                           by flow hash and reduced to one row per flow
  * The device does the parse and the checksums (nexg_parse_batch,
  * NEXG_OUT_RECORD) and the option lists (nexg_decode_options); this header
  * only reads header fields out of the frame bytes at the offsets the device
@@ -894,6 +897,8 @@ inline std::vector<uint8_t> message_bytes(const Icmpv6Packet& p) {
 
 /* ---- flow keys (extension: the reference has no flow notion) --------------- */
 
+using FlowGroup = nexg_flow_group;  // one row of Engine::flow_groups (include/nexg.h)
+
 // nexg_flow_option (include/nexg.h): which key a frame's flow row hashes.
 //   FlowOption().symmetric()        both directions of a conversation get one key
 //   FlowOption().no_ports()         addresses only
@@ -1371,6 +1376,69 @@ class Engine {  // one nexg context on one gfx950 device, one stream
         check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
         for (uint32_t b = 0; b < buckets; b++)
             for (uint64_t k = out.bucket_first[b]; k < out.bucket_first[b + 1]; k++) out.bucket[out.index[k]] = b;
+        return out;
+    }
+
+    // The frame numbers ordered by (flows[i].hash, i) (nexg_flow_sort): a
+    // stable radix sort on the device. out_index: a device array of `count`
+    // entries. Nothing is waited for.
+    void flow_sort(const nexg_flow* flows, uint64_t count, uint32_t* out_index) {
+        DeviceScope ds(device_);
+        const uint64_t wsb = nexg_flow_sort_workspace(count);
+        check(nexg_flow_sort(ctx_, flows, count, out_index, scratch(35, wsb), wsb, stream_), "nexg_flow_sort");
+    }
+
+    // One row per run of equal hashes in `order` (flow_sort's output):
+    // packets, bytes, the first frame, and `mixed`, nonzero where flows with
+    // different keys share the hash (nexg_flow_groups). `out` is a device
+    // array of `cap` rows (16-B aligned), out_group (may be null) a device
+    // array of frames.count group numbers by frame. Returns the number of
+    // groups, which may exceed `cap` (one stream synchronisation).
+    uint64_t flow_groups(const nexg_frames& frames, const nexg_record* records, const nexg_flow* flows,
+                         const uint32_t* order, FlowGroup* out, uint64_t cap, uint32_t* out_group,
+                         const FlowOption& option = {}) {
+        DeviceScope ds(device_);
+        const uint64_t wsb = nexg_flow_groups_workspace(frames.count);
+        void* ws = scratch(36, wsb);
+        uint64_t* d_count = static_cast<uint64_t*>(scratch(37, 8));
+        check(nexg_flow_groups(ctx_, &frames, records, flows, &option.get(), order, out, cap, out_group, d_count, ws, wsb,
+                               stream_),
+              "nexg_flow_groups");
+        uint64_t n = 0;
+        check_hip(hipMemcpyAsync(&n, d_count, 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        return n;
+    }
+
+    // parse (NEXG_OUT_RECORD) + flow + flow_sort + flow_groups of host frames
+    struct FlowGroups {
+        std::vector<FlowGroup> groups;   // ascending by hash
+        std::vector<uint32_t> order;     // frame numbers by (hash, frame number)
+        std::vector<uint32_t> group_of;  // per frame
+    };
+    FlowGroups flow_group_bufs(const std::vector<std::vector<uint8_t>>& frames, const FlowOption& fopt = {},
+                               ParseOption option = {}, ParseMode mode = ParseMode::Lenient) {
+        DeviceScope ds(device_);
+        const uint64_t n = frames.size();
+        FlowGroups out;
+        if (n == 0) return out;
+        HostBatch hb(*this, frames);
+        nexg_record* d_recs = static_cast<nexg_record*>(scratch(3, n * 64));
+        nexg_flow* d_flows = static_cast<nexg_flow*>(scratch(34, n * 8));
+        uint32_t* d_order = static_cast<uint32_t*>(scratch(24, n * 4));
+        uint32_t* d_group = static_cast<uint32_t*>(scratch(38, n * 4));
+        FlowGroup* d_rows = static_cast<FlowGroup*>(scratch(39, n * 32));
+        parse(hb.fb, option, mode, NEXG_OUT_RECORD, d_recs);
+        flow(hb.fb, d_recs, d_flows, fopt);
+        flow_sort(d_flows, n, d_order);
+        const uint64_t g = flow_groups(hb.fb, d_recs, d_flows, d_order, d_rows, n, d_group, fopt);
+        out.groups.resize(g);
+        out.order.resize(n);
+        out.group_of.resize(n);
+        check_hip(hipMemcpyAsync(out.groups.data(), d_rows, g * 32, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipMemcpyAsync(out.order.data(), d_order, n * 4, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipMemcpyAsync(out.group_of.data(), d_group, n * 4, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
         return out;
     }
 

@@ -507,10 +507,31 @@ def flow_partition_workspace(count, buckets):
     return 8 + 4 * ((chunks + 1) & ~1) + 4 * counters
 
 
+# per-flow counters (nexg_flow_sort / nexg_flow_groups)
+FLOW_GROUP_MIXED = 0x1  # nexg_flow_group.flags8 bit 0: mixed != 0
+FLOW_GROUP_DTYPE = np.dtype([("hash", "<u4"), ("kind", "u1"), ("proto", "u1"), ("flags8", "u1"), ("reserved", "u1"),
+                             ("first", "<u4"), ("packets", "<u4"), ("bytes", "<u8"), ("mixed", "<u4"),
+                             ("first_index", "<u4")])
+assert FLOW_GROUP_DTYPE.itemsize == 32
+
+
+def flow_sort_workspace(count):
+    """nexg_flow_sort_workspace: bytes of nexg_flow_sort's workspace."""
+    return flow_partition_workspace(count, 256) + 16 * int(count)
+
+
+def flow_groups_workspace(count):
+    """nexg_flow_groups_workspace: bytes of nexg_flow_groups' workspace."""
+    count = int(count)
+    tiles = (count + 255) // 256
+    return 16 + 8 * tiles + 8 * count + 8 * ((tiles + 1) & ~1) + 4 * ((count + 1) & ~1)
+
+
 #: static inline helpers of include/nexg.h (header-only, not exported)
 HEADER_INLINE = ("nexg_sparse_decode", "nexg_grouped_code", "nexg_grouped_exc_slot", "nexg_offsets32_bases",
                  "nexg_offsets32_bytes", "nexg_decap_select_workspace", "nexg_dns_tile_first_bytes",
-                 "nexg_select_workspace", "nexg_gather_plan_workspace", "nexg_flow_partition_workspace")
+                 "nexg_select_workspace", "nexg_gather_plan_workspace", "nexg_flow_partition_workspace",
+                 "nexg_flow_sort_workspace", "nexg_flow_groups_workspace")
 
 #: every symbol include/nexg.h declares (tests check the .so exports them)
 EXPORTED_SYMBOLS = (
@@ -518,7 +539,7 @@ EXPORTED_SYMBOLS = (
     "nexg_ctx_last_error", "nexg_ctx_cu_count", "nexg_parse_batch", "nexg_checksum_batch", "nexg_decode_options", "nexg_probe_stream",
     "nexg_decap_batch", "nexg_decap_select", "nexg_dns_batch", "nexg_dns_entries",
     "nexg_filter_check", "nexg_select_batch", "nexg_gather_plan", "nexg_gather_frames", "nexg_gather_rows",
-    "nexg_flow_batch", "nexg_flow_partition",
+    "nexg_flow_batch", "nexg_flow_partition", "nexg_flow_sort", "nexg_flow_groups",
     "nexg_probe_span_clock", "nexg_probe_latency",
     "nexg_sparse_expand", "nexg_grouped_expand", "nexg_recompute_checksums_batch",
     "nexg_rx_config_default", "nexg_rx_open", "nexg_rx_next_batch", "nexg_rx_stats", "nexg_rx_close",

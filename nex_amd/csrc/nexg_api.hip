@@ -485,6 +485,53 @@ int nexg_flow_partition(nexg_ctx* ctx, const nexg_frames* frames, const nexg_flo
                       NEXG_ELAUNCH);
 }
 
+int nexg_flow_sort(nexg_ctx* ctx, const nexg_flow* flows, uint64_t count, uint32_t* out_index, void* workspace,
+                   uint64_t workspace_bytes, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "flow_sort: more than 2^32 - 1 frames%s", nullptr);
+    if (count && (!flows || !out_index || !workspace))
+        return fail(ctx, NEXG_EINVAL, "NULL flows, output or workspace%s", nullptr);
+    if (count && workspace_bytes < nexg_flow_sort_workspace(count))
+        return fail(ctx, NEXG_EINVAL, "flow_sort: workspace smaller than nexg_flow_sort_workspace%s", nullptr);
+    if (((reinterpret_cast<uint64_t>(flows) | reinterpret_cast<uint64_t>(workspace)) & 7u) != 0 ||
+        (reinterpret_cast<uint64_t>(out_index) & 3u) != 0)
+        return fail(ctx, NEXG_EINVAL, "misaligned flows, output or workspace%s", nullptr);
+    DeviceGuard g(ctx);
+    return hip_status(ctx, nexg::launch_flow_sort(flows, count, out_index, workspace, static_cast<hipStream_t>(stream)),
+                      NEXG_ELAUNCH);
+}
+
+int nexg_flow_groups(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records, const nexg_flow* flows,
+                     const nexg_flow_option* option, const uint32_t* order, nexg_flow_group* out, uint64_t groups_cap,
+                     uint32_t* out_group, uint64_t* out_count, void* workspace, uint64_t workspace_bytes, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    uint32_t flags = 0u;
+    if (option) {
+        if (option->reserved != 0) return fail(ctx, NEXG_EINVAL, "flow option: reserved must be 0%s", nullptr);
+        if ((option->flags & ~(NEXG_FLOW_SYMMETRIC | NEXG_FLOW_NO_PORTS | NEXG_FLOW_KEY)) != 0)
+            return fail(ctx, NEXG_EINVAL, "flow option: unknown flag bits%s", nullptr);
+        flags = option->flags;
+    }
+    const uint64_t count = frames->count;
+    if (count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "flow_groups: more than 2^32 - 1 frames%s", nullptr);
+    if (!out_count) return fail(ctx, NEXG_EINVAL, "NULL out_count%s", nullptr);
+    if (count && (!records || !flows || !order || !workspace || (groups_cap && !out)))
+        return fail(ctx, NEXG_EINVAL, "NULL records, flows, order, output or workspace%s", nullptr);
+    if (count && workspace_bytes < nexg_flow_groups_workspace(count))
+        return fail(ctx, NEXG_EINVAL, "flow_groups: workspace smaller than nexg_flow_groups_workspace%s", nullptr);
+    if (((reinterpret_cast<uint64_t>(records) | reinterpret_cast<uint64_t>(out)) & 15u) != 0 ||
+        ((reinterpret_cast<uint64_t>(flows) | reinterpret_cast<uint64_t>(out_count) |
+          reinterpret_cast<uint64_t>(workspace)) & 7u) != 0 ||
+        ((reinterpret_cast<uint64_t>(order) | reinterpret_cast<uint64_t>(out_group)) & 3u) != 0)
+        return fail(ctx, NEXG_EINVAL, "misaligned records, flows, order, output or workspace%s", nullptr);
+    const nexg::ParseArgs a = to_args(frames);
+    DeviceGuard g(ctx);
+    return hip_status(ctx, nexg::launch_flow_groups(a, records, flows, flags, order, out, groups_cap, out_group, out_count,
+                                                    workspace, static_cast<hipStream_t>(stream)),
+                      NEXG_ELAUNCH);
+}
+
 int nexg_probe_stream(nexg_ctx* ctx, const void* data, uint64_t bytes, uint32_t out_per_64,
                       void* out, void* stream) {
     if (!ctx) return NEXG_EINVAL;

@@ -5,64 +5,51 @@
 // is one stable radix pass over those rows with up to 256 buckets (a histogram
 // per 1024-frame tile, a hierarchical scan of the histograms, a scatter), the
 // select's count / scan / scatter shape with P counters per tile instead of one.
+// nexg_flow_sort is four such passes over the 32-bit hash with 256 buckets (a
+// stable LSD radix sort of (hash, index) pairs), and nexg_flow_groups reduces
+// the sorted batch to one row per run of equal hashes by prefix sums.
 #include "table_kernels.hpp"
 
 namespace nexg {
 
 static_assert(sizeof(nexg_flow) == 8, "nexg_flow is 8 bytes (include/nexg.h)");
 static_assert(sizeof(nexg_flow_option) == 48, "nexg_flow_option is 48 bytes (include/nexg.h)");
+static_assert(sizeof(nexg_flow_group) == 32, "nexg_flow_group is 32 bytes (include/nexg.h)");
 
 // ---- flow rows -----------------------------------------------------------------------
 
 constexpr uint32_t kFlowNibbles = 72;  // 36 key bytes at most
 
-// k_flow: one lane per frame. The hash is linear over GF(2), so it is the XOR
-// of one table entry per 4-bit nibble of the key bytes: s_tab[p][n] = the XOR
-// of the key windows K[4p + k, 4p + k + 32) over the set bits k of n. The
-// table (72 x 16 words, 4.5 KiB) is built per workgroup from the ten key words
-// (4.5 entries per lane, 4 shift / select / XOR steps each); a lookup reads
-// one of 16 consecutive words, so the 64 lanes of a wave touch 16 distinct
-// banks at most and lanes with equal nibbles share a broadcast: no bank
-// conflict, where a 256-entry byte table would see the lanes' random bytes
-// collide, and the bit-serial form costs three VALU steps per key bit (864 for
-// an IPv6 frame with ports against 72 lookups). Per lane: 48 B of its record
-// (the three 16-B quarters that hold flags / l3_off, ip_word / ip_proto /
-// ip_src, ip_dst / the ports), for an IPv6 frame its two addresses as
-// big-endian words (frame_be_words of table_kernels.hpp), and one 8-B
-// non-temporal store; consecutive lanes write consecutive rows. Words no lane
-// of the wave has (the IPv6 words in a wave of IPv4 frames) are skipped by
-// wave-uniform branches; a lane with a shorter key looks up nibble 0 there,
-// whose entry is 0.
-__global__ __launch_bounds__(256) void k_flow(ParseArgs a, const nexg_record* recs, uint32_t opt, FlowKey key,
-                                              nexg_flow* out) {
-    typedef uint32_t v2u __attribute__((ext_vector_type(2)));
-    __shared__ uint32_t s_key[10];
-    __shared__ uint32_t s_tab[kFlowNibbles * 16u];
-    const uint32_t t = threadIdx.x;
-#pragma unroll
-    for (uint32_t k = 0; k < 10; k++)
-        if (t == k) s_key[k] = key.w[k];
-    __syncthreads();
-    for (uint32_t e = t; e < kFlowNibbles * 16u; e += kTile) {
-        const uint32_t p = e >> 4, n = e & 15u, wi = p >> 3, sh = (p & 7u) * 4u;  // a nibble lies inside one key word
-        const uint64_t kk = (uint64_t)s_key[wi] << 32 | s_key[wi + 1];            // wi <= 8
-        uint32_t v = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < 4; k++)
-            if (n & (8u >> k)) v ^= (uint32_t)((kk << (sh + k)) >> 32);
-        s_tab[e] = v;
+// A frame's flow key as nexg_flow_batch documents it (include/nexg.h): which
+// frames have a flow, the IPv4 fragment rule, the IPv6 addresses out of the
+// frame, the symmetric exchange. k_flow hashes the words; k_group_mark compares
+// them. Per lane: 48 B of its record (the three 16-B quarters that hold flags /
+// l3_off, ip_word / ip_proto / ip_src, ip_dst / the ports) and, for an IPv6
+// frame, its two addresses as big-endian words (frame_be_words of
+// table_kernels.hpp). A lane with `on` false loads nothing and has no flow.
+// ext / l64: table_extent's verdict and len(idx) (false / 0 without `on`).
+struct FlowKeyWords {
+    uint32_t W[9];         // the key bytes as big-endian words: 2 or 3 (IPv4), 8 or 9 (IPv6); 0 past the key
+    uint32_t kind, proto;  // NEXG_FLOW_*; record.ip_proto, 0 without a flow
+    bool has, v6, l4, swapped;
+};
+__device__ __forceinline__ FlowKeyWords flow_key_words(const ParseArgs& a, const nexg_record* recs, uint64_t idx, bool on,
+                                                       uint32_t opt, bool& ext, uint64_t& l64) {
+    RecQuarter<0> q0{make_uint4(0u, 0u, 0u, 0u)};
+    RecQuarter<1> q1{make_uint4(0u, 0u, 0u, 0u)};
+    RecQuarter<2> q2{make_uint4(0u, 0u, 0u, 0u)};
+    uint64_t off = 0;
+    l64 = 0;
+    ext = false;
+    if (on) {
+        q0 = rec_quarter<0>(recs + idx);
+        q1 = rec_quarter<1>(recs + idx);
+        q2 = rec_quarter<2>(recs + idx);
+        ext = table_extent(a, idx, off, l64);
     }
-    __syncthreads();
-    const uint64_t idx = (uint64_t)blockIdx.x * kTile + t;
-    if (idx >= a.count) return;
-    const RecQuarter<0> q0 = rec_quarter<0>(recs + idx);
-    const RecQuarter<1> q1 = rec_quarter<1>(recs + idx);
-    const RecQuarter<2> q2 = rec_quarter<2>(recs + idx);
-    uint64_t off, l64;
-    const bool ext = table_extent(a, idx, off, l64);
     const uint32_t flags = rec_dw<kRecFlags>(q0), l3 = rec_l3(rec_dw<kRecL3>(q0)), ip_word = rec_dw<kRecIpWord>(q1),
                    proto = rec_proto(rec_dw<kRecProto>(q1)), ports_dw = rec_dw<kRecPorts>(q2);
-    const bool ok = rec_status(flags) == 0u;
+    const bool ok = on && rec_status(flags) == 0u;
     const bool v4 = ok && (flags & NEXG_L_IPV4) != 0u;
     // the record is caller memory: the header must lie inside the frame's own extent before any load
     const bool v6 = ok && !v4 && (flags & NEXG_L_IPV6) != 0u && ext && (uint64_t)l3 + 40u <= l64;
@@ -94,9 +81,54 @@ __global__ __launch_bounds__(256) void k_flow(ParseArgs a, const nexg_record* re
         sport = dport, dport = x;
     }
     const uint32_t ports = sport << 16 | dport;
-    // the key bytes as big-endian words: 2 or 3 (IPv4), 8 or 9 (IPv6)
-    const uint32_t W[9] = {S[0], v6 ? S[1] : D[0], v6 ? S[2] : ports, v6 ? S[3] : 0u, v6 ? D[0] : 0u,
-                           v6 ? D[1] : 0u, v6 ? D[2] : 0u, v6 ? D[3] : 0u, v6 ? ports : 0u};
+    const uint32_t kind = v4 ? (l4 ? NEXG_FLOW_IPV4_L4 : NEXG_FLOW_IPV4) : v6 ? (l4 ? NEXG_FLOW_IPV6_L4 : NEXG_FLOW_IPV6)
+                                                                             : NEXG_FLOW_NONE;
+    return {{S[0], v6 ? S[1] : D[0], v6 ? S[2] : ports, v6 ? S[3] : 0u, v6 ? D[0] : 0u, v6 ? D[1] : 0u, v6 ? D[2] : 0u,
+             v6 ? D[3] : 0u, v6 ? ports : 0u},
+            kind, has ? proto : 0u, has, v6, l4, swapped};
+}
+
+// k_flow: one lane per frame. The hash is linear over GF(2), so it is the XOR
+// of one table entry per 4-bit nibble of the key bytes: s_tab[p][n] = the XOR
+// of the key windows K[4p + k, 4p + k + 32) over the set bits k of n. The
+// table (72 x 16 words, 4.5 KiB) is built per workgroup from the ten key words
+// (4.5 entries per lane, 4 shift / select / XOR steps each); a lookup reads
+// one of 16 consecutive words, so the 64 lanes of a wave touch 16 distinct
+// banks at most and lanes with equal nibbles share a broadcast: no bank
+// conflict, where a 256-entry byte table would see the lanes' random bytes
+// collide, and the bit-serial form costs three VALU steps per key bit (864 for
+// an IPv6 frame with ports against 72 lookups). Per lane: flow_key_words'
+// loads and one 8-B non-temporal store; consecutive lanes write consecutive
+// rows. Words no lane of the wave has (the IPv6 words in a wave of IPv4
+// frames) are skipped by wave-uniform branches; a lane with a shorter key
+// looks up nibble 0 there, whose entry is 0.
+__global__ __launch_bounds__(256) void k_flow(ParseArgs a, const nexg_record* recs, uint32_t opt, FlowKey key,
+                                              nexg_flow* out) {
+    typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+    __shared__ uint32_t s_key[10];
+    __shared__ uint32_t s_tab[kFlowNibbles * 16u];
+    const uint32_t t = threadIdx.x;
+#pragma unroll
+    for (uint32_t k = 0; k < 10; k++)
+        if (t == k) s_key[k] = key.w[k];
+    __syncthreads();
+    for (uint32_t e = t; e < kFlowNibbles * 16u; e += kTile) {
+        const uint32_t p = e >> 4, n = e & 15u, wi = p >> 3, sh = (p & 7u) * 4u;  // a nibble lies inside one key word
+        const uint64_t kk = (uint64_t)s_key[wi] << 32 | s_key[wi + 1];            // wi <= 8
+        uint32_t v = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++)
+            if (n & (8u >> k)) v ^= (uint32_t)((kk << (sh + k)) >> 32);
+        s_tab[e] = v;
+    }
+    __syncthreads();
+    const uint64_t idx = (uint64_t)blockIdx.x * kTile + t;
+    if (idx >= a.count) return;
+    bool ext;
+    uint64_t l64;
+    const FlowKeyWords kw = flow_key_words(a, recs, idx, true, opt, ext, l64);
+    const bool has = kw.has, v6 = kw.v6, l4 = kw.l4;
+    const uint32_t(&W)[9] = kw.W;
     uint32_t h = 0;
 #pragma unroll
     for (uint32_t j = 0; j < 9; j++) {
@@ -105,9 +137,7 @@ __global__ __launch_bounds__(256) void k_flow(ParseArgs a, const nexg_record* re
 #pragma unroll
         for (uint32_t q = 0; q < 8; q++) h ^= s_tab[(8u * j + q) * 16u + ((W[j] >> (28u - 4u * q)) & 15u)];
     }
-    const uint32_t kind = v4 ? (l4 ? NEXG_FLOW_IPV4_L4 : NEXG_FLOW_IPV4) : v6 ? (l4 ? NEXG_FLOW_IPV6_L4 : NEXG_FLOW_IPV6)
-                                                                             : NEXG_FLOW_NONE;
-    const uint32_t tail = has ? kind | proto << 8 | (swapped ? 1u << 16 : 0u) : 0u;
+    const uint32_t tail = kw.kind | kw.proto << 8 | (kw.swapped ? 1u << 16 : 0u);
     __builtin_nontemporal_store(v2u{has ? h : 0u, tail}, reinterpret_cast<v2u*>(out) + idx);
 }
 
@@ -146,14 +176,23 @@ __device__ __forceinline__ uint64_t bucket_peers(uint32_t b, bool valid, uint32_
 // bucket's peer count. The LDS serves a wave's accesses in program order, so
 // the next round's leader reads what this round's stored. bk[r] keeps the
 // lane's bucket of round r (0xFFFFFFFF past the table) for phase C.
-__device__ __forceinline__ void wave_hist(const nexg_flow* flows, uint64_t count, uint32_t P, uint32_t nbits,
-                                          uint64_t first, volatile uint32_t* row, uint32_t (&bk)[kPartRounds]) {
+// bucket(idx) is how a lane gets its bucket: PartBucket for the partition,
+// SortDigit (below) for a pass of the sort.
+struct PartBucket {
+    const nexg_flow* flows;
+    uint32_t P;
+    __device__ __forceinline__ uint32_t operator()(uint64_t idx) const { return NEXG_GLOBAL(uint32_t, flows)[idx * 2u] % P; }
+};
+
+template <typename Bucket>
+__device__ __forceinline__ void wave_hist(const Bucket& bucket, uint64_t count, uint32_t nbits, uint64_t first,
+                                          volatile uint32_t* row, uint32_t (&bk)[kPartRounds]) {
     const uint32_t lane = threadIdx.x & 63u;
 #pragma unroll
     for (uint32_t r = 0; r < kPartRounds; r++) {
         const uint64_t idx = first + 64u * r + lane;
         const bool valid = idx < count;
-        const uint32_t b = valid ? NEXG_GLOBAL(uint32_t, flows)[idx * 2u] % P : 0u;
+        const uint32_t b = valid ? bucket(idx) : 0u;
         bk[r] = valid ? b : 0xFFFFFFFFu;
         const uint64_t m = bucket_peers(b, valid, nbits);
         const uint32_t cnt = (uint32_t)__builtin_popcountll(m);
@@ -170,7 +209,8 @@ __global__ __launch_bounds__(256) void k_part_count(const nexg_flow* flows, uint
     for (uint32_t k = 0; k < 4; k++) s_w[k][t] = 0u;
     __syncthreads();
     uint32_t bk[kPartRounds];
-    wave_hist(flows, count, P, nbits, (uint64_t)blockIdx.x * kPartTile + (uint64_t)wv * (kPartTile / 4u), s_w[wv], bk);
+    wave_hist(PartBucket{flows, P}, count, nbits, (uint64_t)blockIdx.x * kPartTile + (uint64_t)wv * (kPartTile / 4u),
+              s_w[wv], bk);
     __syncthreads();
     if (t < P) hist[(uint64_t)t * T + blockIdx.x] = s_w[0][t] + s_w[1][t] + s_w[2][t] + s_w[3][t];
 }
@@ -218,14 +258,13 @@ __global__ __launch_bounds__(256) void k_chunk_apply(uint32_t* v, uint64_t n, co
 // position in LDS, and after one more barrier consecutive lanes take
 // consecutive positions: a bucket's frames of this tile leave as one run of
 // consecutive entries per output array (128 entries long at 8 buckets, 4 at
-// 256) instead of one isolated store per frame and array.
-__global__ __launch_bounds__(256) void k_part_scatter(ParseArgs a, const nexg_flow* flows, uint32_t P, uint32_t nbits,
-                                                      uint64_t T, const uint32_t* base, uint32_t* out_index,
-                                                      uint64_t* out_off, uint32_t* out_len, uint64_t* bucket_first) {
-    __shared__ uint32_t s_w[4][256];
-    __shared__ uint32_t s_ord[kPartTile];  // frame number in the tile | bucket << 16, in the tile's bucket order
-    __shared__ uint32_t s_delta[256];      // global position - position in the tile's order, per bucket
-    __shared__ uint32_t s_ws[4];
+// 256) instead of one isolated store per frame and array. tile_bucket_order is
+// all of that up to the parked order (s_ord, s_delta), for the partition and
+// for the sort's passes alike; it returns the lane's bucket's global base.
+template <typename Bucket>
+__device__ __forceinline__ uint32_t tile_bucket_order(const Bucket& bucket, uint64_t count, uint32_t P, uint32_t nbits,
+                                                      uint64_t T, const uint32_t* base, uint32_t (*s_w)[256],
+                                                      uint32_t* s_ord, uint32_t* s_delta, uint32_t* s_ws) {
     const uint32_t t = threadIdx.x, wv = t >> 6, lane = t & 63u;
 #pragma unroll
     for (uint32_t k = 0; k < 4; k++) s_w[k][t] = 0u;
@@ -234,23 +273,19 @@ __global__ __launch_bounds__(256) void k_part_scatter(ParseArgs a, const nexg_fl
     __syncthreads();
     const uint64_t tile0 = (uint64_t)blockIdx.x * kPartTile;
     uint32_t bk[kPartRounds];
-    wave_hist(flows, a.count, P, nbits, tile0 + (uint64_t)wv * (kPartTile / 4u), s_w[wv], bk);
+    wave_hist(bucket, count, nbits, tile0 + (uint64_t)wv * (kPartTile / 4u), s_w[wv], bk);
     __syncthreads();
-    {
-        uint32_t c[4], tot = 0;
+    uint32_t c[4], tot = 0;
 #pragma unroll
-        for (uint32_t k = 0; k < 4; k++) c[k] = s_w[k][t], tot += c[k];  // 0 for t >= P
-        uint32_t frames;
-        uint32_t run = block_excl_scan(tot, s_ws, frames);  // the bucket's first position in the tile's order
-        const uint32_t b0 = t < P ? base[(uint64_t)t * T + blockIdx.x] : 0u;
-        s_delta[t] = b0 - run;
+    for (uint32_t k = 0; k < 4; k++) c[k] = s_w[k][t], tot += c[k];  // 0 for t >= P
+    uint32_t frames;
+    uint32_t run = block_excl_scan(tot, s_ws, frames);  // the bucket's first position in the tile's order
+    const uint32_t b0 = t < P ? base[(uint64_t)t * T + blockIdx.x] : 0u;
+    s_delta[t] = b0 - run;
 #pragma unroll
-        for (uint32_t k = 0; k < 4; k++) {
-            s_w[k][t] = run;
-            run += c[k];
-        }
-        if (blockIdx.x == 0 && t < P) bucket_first[t] = b0;  // tile 0's base: the frames in the buckets below
-        if (blockIdx.x == 0 && t == 0) bucket_first[P] = a.count;
+    for (uint32_t k = 0; k < 4; k++) {
+        s_w[k][t] = run;
+        run += c[k];
     }
     __syncthreads();
     volatile uint32_t* row = s_w[wv];
@@ -267,6 +302,21 @@ __global__ __launch_bounds__(256) void k_part_scatter(ParseArgs a, const nexg_fl
         }
     }
     __syncthreads();
+    return b0;
+}
+
+__global__ __launch_bounds__(256) void k_part_scatter(ParseArgs a, const nexg_flow* flows, uint32_t P, uint32_t nbits,
+                                                      uint64_t T, const uint32_t* base, uint32_t* out_index,
+                                                      uint64_t* out_off, uint32_t* out_len, uint64_t* bucket_first) {
+    __shared__ uint32_t s_w[4][256];
+    __shared__ uint32_t s_ord[kPartTile];  // frame number in the tile | bucket << 16, in the tile's bucket order
+    __shared__ uint32_t s_delta[256];      // global position - position in the tile's order, per bucket
+    __shared__ uint32_t s_ws[4];
+    const uint32_t t = threadIdx.x;
+    const uint64_t tile0 = (uint64_t)blockIdx.x * kPartTile;
+    const uint32_t b0 = tile_bucket_order(PartBucket{flows, P}, a.count, P, nbits, T, base, s_w, s_ord, s_delta, s_ws);
+    if (blockIdx.x == 0 && t < P) bucket_first[t] = b0;  // tile 0's base: the frames in the buckets below
+    if (blockIdx.x == 0 && t == 0) bucket_first[P] = a.count;
 #pragma unroll
     for (uint32_t r = 0; r < kPartRounds; r++) {
         const uint32_t j = r * kTile + t, e = s_ord[j];
@@ -306,6 +356,238 @@ hipError_t launch_flow_partition(const ParseArgs& a, const nexg_flow* flows, uin
     hipLaunchKernelGGL(k_chunk_apply, dim3((uint32_t)chunks), dim3(kTile), 0, s, hist, n, sums);
     hipLaunchKernelGGL(k_part_scatter, dim3((uint32_t)T), dim3(kTile), 0, s, a, flows, buckets, nbits, T, hist, out_index,
                        out_off, out_len, bucket_first);
+    return hipGetLastError();
+}
+
+// ---- sort --------------------------------------------------------------------------------
+// Four passes of the partition's count / scan / scatter with 256 buckets, one
+// per byte of the hash from the lowest up: a stable LSD radix sort. What moves
+// is a (hash, index) pair in one u64 (hash low, frame number high); the first
+// pass makes the pairs from the flow rows, the last stores the frame numbers
+// alone. The workspace is the partition's at 256 buckets, then two buffers of
+// `count` pairs (nexg_flow_sort_workspace).
+
+template <bool kFirst>
+struct SortDigit {
+    const void* src;  // kFirst: the flow rows; else the pairs the pass before stored
+    uint32_t shift;
+    __device__ __forceinline__ uint64_t pair(uint64_t idx) const {
+        const uint64_t v = NEXG_GLOBAL(uint64_t, src)[idx];
+        return kFirst ? (v & 0xFFFFFFFFull) | idx << 32 : v;
+    }
+    __device__ __forceinline__ uint32_t operator()(uint64_t idx) const { return ((uint32_t)pair(idx) >> shift) & 255u; }
+};
+
+// k_part_count with the pass's digit as the bucket
+template <bool kFirst>
+__global__ __launch_bounds__(256) void k_sort_count(const void* src, uint64_t count, uint32_t shift, uint64_t T,
+                                                    uint32_t* hist) {
+    __shared__ uint32_t s_w[4][256];
+    const uint32_t t = threadIdx.x, wv = t >> 6;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; k++) s_w[k][t] = 0u;
+    __syncthreads();
+    uint32_t bk[kPartRounds];
+    wave_hist(SortDigit<kFirst>{src, shift}, count, 8u, (uint64_t)blockIdx.x * kPartTile + (uint64_t)wv * (kPartTile / 4u),
+              s_w[wv], bk);
+    __syncthreads();
+    hist[(uint64_t)t * T + blockIdx.x] = s_w[0][t] + s_w[1][t] + s_w[2][t] + s_w[3][t];
+}
+
+// k_part_scatter's shape: a digit's pairs of this tile leave as one run of
+// consecutive 8-B entries (kLast: 4-B frame numbers). A pair is loaded a second
+// time for the store (its tile's 8 KiB were read a moment ago); whatever the
+// source holds by then, the position comes from the parked order and is
+// checked against `count`.
+template <bool kFirst, bool kLast>
+__global__ __launch_bounds__(256) void k_sort_scatter(const void* src, uint64_t count, uint32_t shift, uint64_t T,
+                                                      const uint32_t* base, uint64_t* dst, uint32_t* out_index) {
+    __shared__ uint32_t s_w[4][256];
+    __shared__ uint32_t s_ord[kPartTile];
+    __shared__ uint32_t s_delta[256];
+    __shared__ uint32_t s_ws[4];
+    const uint32_t t = threadIdx.x;
+    const uint64_t tile0 = (uint64_t)blockIdx.x * kPartTile;
+    const SortDigit<kFirst> digit{src, shift};
+    tile_bucket_order(digit, count, 256u, 8u, T, base, s_w, s_ord, s_delta, s_ws);
+#pragma unroll
+    for (uint32_t r = 0; r < kPartRounds; r++) {
+        const uint32_t j = r * kTile + t, e = s_ord[j];
+        if (e != 0xFFFFFFFFu) {
+            const uint64_t pair = digit.pair(tile0 + (e & 0xFFFFu));
+            const uint32_t pos = j + s_delta[e >> 16];
+            if (pos < count) {
+                if (kLast)
+                    out_index[pos] = (uint32_t)(pair >> 32);
+                else
+                    dst[pos] = pair;
+            }
+        }
+    }
+}
+
+hipError_t launch_flow_sort(const nexg_flow* flows, uint64_t count, uint32_t* out_index, void* workspace, hipStream_t s) {
+    if (count == 0) return hipSuccess;
+    const uint64_t T = (count + kPartTile - 1) / kPartTile, n = T * 256u;
+    const uint64_t chunks = (n + kScanChunk - 1) / kScanChunk;
+    // the workspace as nexg_flow_sort_workspace lays it out
+    uint64_t* total = static_cast<uint64_t*>(workspace);
+    uint32_t* sums = reinterpret_cast<uint32_t*>(total + 1);
+    uint32_t* hist = sums + ((chunks + 1u) & ~1ull);
+    uint64_t* ping = reinterpret_cast<uint64_t*>(hist + n);
+    uint64_t* pong = ping + count;
+    const dim3 gT((uint32_t)T), gC((uint32_t)chunks), b(kTile);
+    for (uint32_t pass = 0; pass < 4; pass++) {
+        const void* src = pass == 0 ? static_cast<const void*>(flows) : (pass & 1u) ? ping : pong;
+        uint64_t* dst = (pass & 1u) ? pong : ping;
+        const uint32_t shift = 8u * pass;
+        if (pass == 0)
+            hipLaunchKernelGGL(k_sort_count<true>, gT, b, 0, s, src, count, shift, T, hist);
+        else
+            hipLaunchKernelGGL(k_sort_count<false>, gT, b, 0, s, src, count, shift, T, hist);
+        hipLaunchKernelGGL(k_chunk_sums, gC, b, 0, s, hist, n, sums);
+        hipLaunchKernelGGL(k_tile_scan<uint32_t>, dim3(1), b, 0, s, sums, chunks, total);
+        hipLaunchKernelGGL(k_chunk_apply, gC, b, 0, s, hist, n, sums);
+        if (pass == 0)
+            hipLaunchKernelGGL((k_sort_scatter<true, false>), gT, b, 0, s, src, count, shift, T, hist, dst, out_index);
+        else if (pass < 3)
+            hipLaunchKernelGGL((k_sort_scatter<false, false>), gT, b, 0, s, src, count, shift, T, hist, dst, out_index);
+        else
+            hipLaunchKernelGGL((k_sort_scatter<false, true>), gT, b, 0, s, src, count, shift, T, hist, dst, out_index);
+    }
+    return hipGetLastError();
+}
+
+// ---- groups ------------------------------------------------------------------------------
+// One row per run of equal hashes in the sorted order. k_group_mark gives
+// every sorted position a head flag (the hash differs from the position
+// before, or position 0), a break flag (same hash, another key) and its
+// frame's length, and scans the three inside its 256-position tile; one
+// workgroup scans the tiles' totals (k_tile_scan, once per value);
+// k_group_place numbers the groups and notes where each starts; k_group_rows,
+// one lane per group, takes the differences of the prefixes at the group's
+// start and at the next group's. Every step is per position or per group: the
+// sizes of the groups do not enter.
+
+// what k_group_mark leaves per position: the exclusive in-tile prefixes of the
+// lengths (at most 255 x 65535 < 2^24), of the breaks and of the heads (at
+// most 255 each), and the head flag
+constexpr uint32_t kMarkBrk = 24, kMarkHeads = 32, kMarkHead = 40;
+// the three values in one u64 for the tile's scan: 256 x 65535 < 2^24, then two
+// counts of at most 256
+constexpr uint32_t kSumBrk = 24, kSumHeads = 34;
+
+__device__ __forceinline__ bool flow_keys_differ(const FlowKeyWords& x, const FlowKeyWords& y) {
+    uint32_t d = (x.kind ^ y.kind) | (x.proto ^ y.proto);
+#pragma unroll
+    for (uint32_t j = 0; j < 9; j++) d |= x.W[j] ^ y.W[j];
+    return d != 0u;
+}
+
+// `order` is caller memory: an entry past the table stands for a frame with an
+// all-zero flow row, no key and length 0, and nothing is loaded for it. The
+// key of the position before is recomputed, not exchanged: a lane needs it only
+// when the two hashes are equal.
+__global__ __launch_bounds__(256) void k_group_mark(ParseArgs a, const nexg_record* recs, const nexg_flow* flows,
+                                                    uint32_t opt, const uint32_t* order, uint64_t* mark,
+                                                    uint32_t* tile_heads, uint32_t* tile_brk, uint64_t* tile_bytes) {
+    __shared__ uint64_t s_w[4];
+    const uint64_t k = (uint64_t)blockIdx.x * kTile + threadIdx.x;
+    const bool in = k < a.count, prev = in && k > 0;
+    const uint32_t i = in ? order[k] : 0xFFFFFFFFu, j = prev ? order[k - 1] : 0xFFFFFFFFu;
+    const bool vi = in && i < a.count, vj = prev && j < a.count;
+    const uint32_t hi = vi ? NEXG_GLOBAL(uint32_t, flows)[(uint64_t)i * 2u] : 0u;
+    const uint32_t hj = vj ? NEXG_GLOBAL(uint32_t, flows)[(uint64_t)j * 2u] : 0u;
+    const bool head = in && (!prev || hi != hj);
+    bool ext, ext_j;
+    uint64_t l64, l64_j;
+    const FlowKeyWords ki = flow_key_words(a, recs, i, vi, opt, ext, l64);
+    const FlowKeyWords kj = flow_key_words(a, recs, j, vj && !head, opt, ext_j, l64_j);
+    const bool brk = in && !head && flow_keys_differ(ki, kj);
+    const uint64_t len = ext ? l64 : 0u;  // <= 65535 with a valid extent
+    uint64_t total;
+    const uint64_t before = block_excl_scan(len | (uint64_t)brk << kSumBrk | (uint64_t)head << kSumHeads, s_w, total);
+    if (in)
+        mark[k] = (before & 0xFFFFFFull) | ((before >> kSumBrk) & 0xFFull) << kMarkBrk |
+                  ((before >> kSumHeads) & 0xFFull) << kMarkHeads | (uint64_t)head << kMarkHead;
+    if (threadIdx.x == 0) {
+        tile_bytes[blockIdx.x] = total & 0xFFFFFFull;
+        tile_brk[blockIdx.x] = (uint32_t)(total >> kSumBrk) & 0x3FFu;
+        tile_heads[blockIdx.x] = (uint32_t)(total >> kSumHeads);
+    }
+}
+
+// the group number of every position (the heads at and before it, less one),
+// stored by frame number, and each group's first position
+__global__ __launch_bounds__(256) void k_group_place(uint64_t count, const uint32_t* order, const uint64_t* mark,
+                                                     const uint32_t* tile_heads, uint32_t* starts, uint32_t* out_group) {
+    const uint64_t k = (uint64_t)blockIdx.x * kTile + threadIdx.x;
+    if (k >= count) return;
+    const uint64_t m = mark[k];
+    const uint32_t head = (uint32_t)(m >> kMarkHead) & 1u;
+    const uint32_t g = tile_heads[blockIdx.x] + ((uint32_t)(m >> kMarkHeads) & 0xFFu) + head - 1u;
+    // g <= k by construction; checked all the same, as the workspace is caller memory
+    if (head && g < count) starts[g] = (uint32_t)k;
+    if (out_group) {
+        const uint32_t i = order[k];
+        if (i < count) out_group[i] = g;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_group_rows(uint64_t count, const nexg_flow* flows,
+                                                    const uint32_t* order, const uint64_t* mark, const uint32_t* tile_brk,
+                                                    const uint64_t* tile_bytes, const uint64_t* totals,
+                                                    const uint32_t* starts, const uint64_t* out_count, nexg_flow_group* out,
+                                                    uint64_t cap) {
+    const uint64_t g = (uint64_t)blockIdx.x * kTile + threadIdx.x;
+    uint64_t G = *out_count;
+    if (G > count) G = count;
+    if (g >= G || g >= cap) return;
+    // positions out of the workspace are clamped before they index anything
+    uint64_t first = starts[g], next = g + 1 < G ? starts[g + 1] : count;
+    if (first >= count) first = count - 1u;
+    if (next > count) next = count;
+    const uint64_t m0 = mark[first];
+    uint64_t bytes0 = tile_bytes[first >> 8] + (m0 & 0xFFFFFFull), bytes1 = totals[1];
+    uint32_t brk0 = tile_brk[first >> 8] + ((uint32_t)(m0 >> kMarkBrk) & 0xFFu), brk1 = (uint32_t)totals[0];
+    if (next < count) {
+        const uint64_t m1 = mark[next];
+        bytes1 = tile_bytes[next >> 8] + (m1 & 0xFFFFFFull);
+        brk1 = tile_brk[next >> 8] + ((uint32_t)(m1 >> kMarkBrk) & 0xFFu);
+    }
+    const uint32_t fi = order[first];
+    const uint64_t row = fi < count ? NEXG_GLOBAL(uint64_t, flows)[fi] : 0ull;
+    const uint64_t bytes = bytes1 - bytes0;
+    const uint32_t mixed = brk1 - brk0;
+    uint4* o = reinterpret_cast<uint4*>(out + g);
+    o[0] = make_uint4((uint32_t)row, ((uint32_t)(row >> 32) & 0xFFFFu) | (mixed != 0u ? 1u << 16 : 0u), (uint32_t)first,
+                      (uint32_t)(next - first));
+    o[1] = make_uint4((uint32_t)bytes, (uint32_t)(bytes >> 32), mixed, fi);
+}
+
+hipError_t launch_flow_groups(const ParseArgs& a, const nexg_record* recs, const nexg_flow* flows, uint32_t opt,
+                              const uint32_t* order, nexg_flow_group* out, uint64_t groups_cap, uint32_t* out_group,
+                              uint64_t* out_count, void* workspace, hipStream_t s) {
+    const uint64_t count = a.count;
+    if (count == 0) return hipMemsetAsync(out_count, 0, 8, s);
+    const uint64_t tiles = (count + kTile - 1) / kTile, tp = (tiles + 1u) & ~1ull;
+    // the workspace as nexg_flow_groups_workspace lays it out
+    uint64_t* totals = static_cast<uint64_t*>(workspace);  // breaks, bytes
+    uint64_t* tile_bytes = totals + 2;
+    uint64_t* mark = tile_bytes + tiles;
+    uint32_t* tile_heads = reinterpret_cast<uint32_t*>(mark + count);
+    uint32_t* tile_brk = tile_heads + tp;
+    uint32_t* starts = tile_brk + tp;
+    const dim3 gT((uint32_t)tiles), b(kTile);
+    hipLaunchKernelGGL(k_group_mark, gT, b, 0, s, a, recs, flows, opt, order, mark, tile_heads, tile_brk, tile_bytes);
+    hipLaunchKernelGGL(k_tile_scan<uint32_t>, dim3(1), b, 0, s, tile_heads, tiles, out_count);
+    hipLaunchKernelGGL(k_tile_scan<uint32_t>, dim3(1), b, 0, s, tile_brk, tiles, totals);
+    hipLaunchKernelGGL(k_tile_scan<uint64_t>, dim3(1), b, 0, s, tile_bytes, tiles, totals + 1);
+    hipLaunchKernelGGL(k_group_place, gT, b, 0, s, count, order, mark, tile_heads, starts, out_group);
+    const uint64_t rows = groups_cap < count ? groups_cap : count;
+    if (rows)
+        hipLaunchKernelGGL(k_group_rows, dim3((uint32_t)((rows + kTile - 1) / kTile)), b, 0, s, count, flows, order,
+                           mark, tile_brk, tile_bytes, totals, starts, out_count, out, groups_cap);
     return hipGetLastError();
 }
 

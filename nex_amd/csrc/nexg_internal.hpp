@@ -155,6 +155,12 @@ hipError_t launch_flow(const ParseArgs& a, const nexg_record* recs, uint32_t opt
 hipError_t launch_flow_partition(const ParseArgs& a, const nexg_flow* flows, uint32_t buckets, uint32_t* out_index,
                                  uint64_t* out_off, uint32_t* out_len, uint64_t* bucket_first, void* workspace,
                                  hipStream_t s);
+// nexg_flow_sort / nexg_flow_groups (nexg_flow.hip); the workspaces as
+// nexg_flow_sort_workspace / nexg_flow_groups_workspace lay them out
+hipError_t launch_flow_sort(const nexg_flow* flows, uint64_t count, uint32_t* out_index, void* workspace, hipStream_t s);
+hipError_t launch_flow_groups(const ParseArgs& a, const nexg_record* recs, const nexg_flow* flows, uint32_t opt,
+                              const uint32_t* order, nexg_flow_group* out, uint64_t groups_cap, uint32_t* out_group,
+                              uint64_t* out_count, void* workspace, hipStream_t s);
 
 hipError_t launch_probe_stream(const uint8_t* data, uint64_t tiles, uint32_t mode, void* out, hipStream_t s);
 hipError_t launch_probe_latency(uint32_t* buf, uint32_t lines, uint32_t start, uint32_t steps, uint32_t loaded_wgs,

@@ -507,6 +507,79 @@ class Engine:
         return FrameBatch(data=table.data, count=hi - lo, offsets=table.offsets[lo:hi], lengths=table.lengths[lo:hi],
                           hints=table.bucket_hints | table.hints)
 
+    def flow_sort(self, flows, stream=None):
+        """The frame numbers of a batch ordered by (flows[i].hash ascending,
+        frame number ascending) (nexg_flow_sort): a stable radix sort on the
+        device, so every flow is one contiguous run and frames without a flow
+        (hash 0) come first. `flows` is the tensor Engine.flow returned.
+        Returns an int32 device tensor (bit patterns of u32) of `count`
+        entries. Allocates the workspace; no synchronisation."""
+        torch = _torch()
+        count = flows.numel() * flows.element_size() // 8
+        dev = self.torch_device
+        idx = torch.empty(max(count, 1), dtype=torch.int32, device=dev)
+        ws_bytes = abi.flow_sort_workspace(count)
+        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+        self._check(self.lib.nexg_flow_sort(self.ctx, _ptr(flows), count, _ptr(idx), _ptr(ws), ws_bytes,
+                                            self._stream(stream)))
+        return idx[:count]
+
+    def flow_groups(self, batch: FrameBatch, records, flows, option=None, order=None, groups_cap=None, stream=None):
+        """Per-flow counters of a batch (nexg_flow_groups): one row per run of
+        equal hashes in the sorted order, with its packets, its bytes, its
+        first frame and `mixed`, the number of members whose flow key differs
+        from the member before them (nonzero only where two flows share one
+        32-bit hash; the members order[first: first + packets] tell them
+        apart). `records` and `flows` are the tensors Engine.parse
+        (NEXG_OUT_RECORD) and Engine.flow returned for `batch`, `option` the
+        FlowOption given to Engine.flow, `order` Engine.flow_sort's tensor
+        (None: sorted here). Returns (groups, group_of, n_groups, order):
+        groups a uint8 device tensor holding nexg_flow_group[n_groups]
+        (abi.FLOW_GROUP_DTYPE), group_of an int32 device tensor with the group
+        number of every frame, n_groups an int. The rows are sized by reading
+        the group count back (one synchronisation of the stream) and the pass
+        runs once more to fill them; with `groups_cap` given it runs once,
+        rows at or past the capacity are not stored, and n_groups may exceed it.
+
+        The recipe for a flow table of one batch:
+
+            rec = eng.parse(batch, out_kind=abi.OUT_RECORD)
+            flows = eng.flow(batch, rec, FlowOption(symmetric=True))
+            groups, group_of, n, order = eng.flow_groups(batch, rec, flows, FlowOption(symmetric=True))
+            first_index = groups.view(torch.int32).view(-1, 8)[:, 7]
+            first_rec = eng.gather_rows(rec, 64, first_index)     # each flow's first record
+        """
+        from .flow import FlowOption
+        torch = _torch()
+        fo = (option if option is not None else FlowOption()).to_c()  # ValueError for what nexg_flow_groups rejects
+        count = batch.count
+        dev = self.torch_device
+        if order is None:
+            order = self.flow_sort(flows, stream)
+        group_of = torch.empty(max(count, 1), dtype=torch.int32, device=dev)
+        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        ws_bytes = abi.flow_groups_workspace(count)
+        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+        fr = batch.to_c()
+        s = self._stream(stream)
+
+        def run(rows, cap, gof):
+            self._check(self.lib.nexg_flow_groups(self.ctx, ctypes.byref(fr), _ptr(records), _ptr(flows), ctypes.byref(fo),
+                                                  _ptr(order), _ptr(rows), cap, _ptr(gof), _ptr(cnt), _ptr(ws), ws_bytes, s))
+
+        if groups_cap is not None:
+            cap = int(groups_cap)
+            groups = torch.empty(max(cap, 1) * 32, dtype=torch.uint8, device=dev)
+            run(groups, cap, group_of)
+            n = int(cnt.item())  # waits for the kernels
+            return groups[: min(n, cap) * 32], group_of[:count], n, order
+        run(None, 0, group_of)  # the count and the group numbers
+        n = int(cnt.item())  # waits for the kernels
+        groups = torch.empty(max(n, 1) * 32, dtype=torch.uint8, device=dev)
+        if n:
+            run(groups, n, None)
+        return groups[: n * 32], group_of[:count], n, order
+
     def dns(self, batch: FrameBatch, records, port: int = abi.DNS_PORT, any_udp: bool = False, entries_cap=None,
             stream=None):
         """Walk every DNS message of `batch` in place (nexg_dns_batch +

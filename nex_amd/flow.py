@@ -1,11 +1,14 @@
-"""Flow keys, the Toeplitz RSS hash and the flow-affine partition
-(nexg_flow_batch / nexg_flow_partition, include/nexg.h; an extension: the
-reference has no flow notion).
+"""Flow keys, the Toeplitz RSS hash, the flow-affine partition and the
+per-flow counters (nexg_flow_batch / nexg_flow_partition / nexg_flow_sort /
+nexg_flow_groups, include/nexg.h; an extension: the reference has no flow
+notion).
 
-FlowOption is the host form of struct nexg_flow_option. toeplitz, flow_host
-and partition_host restate the header's specification in plain Python: the
-GPU kernels are tested against them, and they are themselves pinned by the
-published RSS verification vectors (tests/golden/flow_vectors.json)."""
+FlowOption is the host form of struct nexg_flow_option. toeplitz, flow_host,
+partition_host, sort_host and groups_host restate the header's specification
+in plain Python: the GPU kernels are tested against them, and they are
+themselves pinned by the published RSS verification vectors
+(tests/golden/flow_vectors.json) and an independent group-by
+(tests/test_flow_groups_host.py)."""
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
@@ -132,3 +135,58 @@ def partition_host(hashes, buckets: int):
     first = np.zeros(buckets + 1, np.int64)
     first[1:] = np.cumsum(np.bincount(b, minlength=buckets))
     return index, first
+
+
+def sort_host(hashes):
+    """nexg_flow_sort on the host: the frame numbers (u32 [count]) ordered by
+    (hash ascending, frame number ascending)."""
+    return np.argsort(np.asarray(hashes, np.uint32), kind="stable").astype(np.uint32)
+
+
+def groups_host(frames: Sequence[Optional[bytes]], records, lengths: Sequence[int], flows,
+                option: FlowOption = FlowOption(), order=None):
+    """nexg_flow_groups on the host: (groups, group_of, n_groups) with groups
+    an abi.FLOW_GROUP_DTYPE array of one row per maximal run of equal
+    flows[order[k]].hash in `order` (None: sort_host of the hashes), group_of
+    (u32 [count]) the group number of every frame that `order` names (others
+    keep 0xFFFFFFFF). frames / records / lengths as flows_host takes them: a
+    frame is None when its extent is not inside the batch's data, and then (or
+    with a length over 65535) it adds nothing to `bytes`. An order entry past
+    the batch is a frame with an all-zero flow row, no key and length 0."""
+    count = len(frames)
+    flows = np.asarray(flows).view(abi.FLOW_DTYPE).reshape(-1)
+    order = sort_host(flows["hash"]) if order is None else np.asarray(order, np.uint32)
+    none = (abi.FLOW_NONE, 0, b"")
+    zero = np.zeros(1, abi.FLOW_DTYPE)[0]
+    keys = {}
+
+    def member(i):
+        """(flow row, key, length) of order entry i"""
+        if i >= count:
+            return zero, none, 0
+        if i not in keys:
+            kind, proto, _, key = flow_key(frames[i], records[i], int(lengths[i]), option)
+            keys[i] = none if kind == abi.FLOW_NONE else (kind, proto, key)
+        ln = int(lengths[i])
+        return flows[i], keys[i], ln if frames[i] is not None and ln <= 65535 else 0
+
+    rows = []
+    group_of = np.full(count, 0xFFFFFFFF, np.uint32)
+    prev = None
+    for k, i in enumerate(int(x) for x in order[:count]):
+        row, key, ln = member(i)
+        if prev is None or int(row["hash"]) != prev[0]:
+            rows.append(dict(hash=int(row["hash"]), kind=int(row["kind"]), proto=int(row["proto"]), first=k, packets=0,
+                             bytes=0, mixed=0, first_index=i))
+        elif key != prev[1]:
+            rows[-1]["mixed"] += 1
+        rows[-1]["packets"] += 1
+        rows[-1]["bytes"] += ln
+        if i < count:
+            group_of[i] = len(rows) - 1
+        prev = (int(row["hash"]), key)
+    out = np.zeros(len(rows), abi.FLOW_GROUP_DTYPE)
+    for g, r in enumerate(rows):
+        out[g] = (r["hash"], r["kind"], r["proto"], abi.FLOW_GROUP_MIXED if r["mixed"] else 0, 0, r["first"], r["packets"],
+                  r["bytes"], r["mixed"], r["first_index"])
+    return out, group_of, len(rows)

@@ -25,7 +25,15 @@ three steps' own times come from a kernel trace of a --quick run:
 which prints, per kernel and per bucket count (the dispatch order of a --quick
 run), the median duration, the step it belongs to and the step's bytes.
 
-usage: python tools/flow_rate.py [--frames N] [--repeats R] [--quick] [--steps-from CSV]
+--groups adds the per-flow counters on the same batch: nexg_flow_sort (with
+the bytes of each of its four passes, and its time as a multiple of four
+256-bucket partitions) and nexg_flow_groups at three flow populations: the
+batch's own flows, and 1000 and 2^20 made-up hashes over the same records
+(their members dealt round-robin over the batch, so the sort has work to do
+and every group but the batch's own is a collision of many keys), each
+against the stream ceiling per byte moved.
+
+usage: python tools/flow_rate.py [--frames N] [--repeats R] [--quick] [--groups] [--steps-from CSV]
 """
 import argparse
 import csv
@@ -42,6 +50,7 @@ sys.path.insert(0, ROOT)
 BUCKETS = (8, 256)
 STEP_OF = {"k_part_count": "count", "k_chunk_sums": "scan", "k_tile_scan": "scan", "k_chunk_apply": "scan",
            "k_part_scatter": "scatter"}
+GROUP_KERNELS = ("k_sort_count", "k_sort_scatter", "k_group_mark", "k_group_place", "k_group_rows")
 
 
 def timed(fn, stream, warmup, steps, repeats):
@@ -70,6 +79,32 @@ def step_bytes(n, buckets):
             "scatter": 8 * n + 4 * n + 4 * counters + 16 * n}
 
 
+def sort_pass_bytes(n):
+    """Algorithmic bytes of the sort's four passes for n frames: a pass is the
+    partition at 256 buckets on 8-B pairs (the first reads the flow rows, 8 B
+    as well); its scatter writes 8 B per frame, the last one 4 B."""
+    from nex_amd import abi
+    counters = (n + abi.FLOW_TILE - 1) // abi.FLOW_TILE * 256
+    chunks = (counters + 1023) // 1024
+    return [{"count": 8 * n + 4 * counters, "scan": 3 * 4 * counters + 3 * 4 * chunks,
+             "scatter": 8 * n + 4 * counters + (4 if p == 3 else 8) * n} for p in range(4)]
+
+
+def groups_step_bytes(n, groups, v6_frames):
+    """Algorithmic bytes of nexg_flow_groups for n frames in `groups` groups:
+    mark reads 4 B of order, the 8-B flow row, the 64-B record and 4 B of
+    offset table per position (plus 32 B of addresses per IPv6 frame), the
+    record, table entry and addresses once more for every position that is not
+    a group's first (the key of the position before), and writes 8 B; the
+    three one-workgroup scans read and write 16 B per 256 positions; place
+    reads 12 B and writes 4 B per position and 4 B per group; rows reads
+    36 B and writes 32 B per group."""
+    tiles = (n + 255) // 256
+    per_key = 64 + 4 + 32 * v6_frames / max(n, 1)
+    return {"mark": int(n * (4 + 8 + 8) + (2 * n - groups) * per_key), "scans": 2 * 16 * tiles,
+            "place": 16 * n + 4 * groups, "rows": 68 * groups}
+
+
 def steps_from(path, frames):
     """Median duration per partition kernel and bucket count from a kernel
     trace of a --quick run (dispatches alternate per bucket count in BUCKETS
@@ -78,7 +113,7 @@ def steps_from(path, frames):
     with open(path) as f:
         for r in csv.DictReader(f):
             name = r["Kernel_Name"]
-            for k in list(STEP_OF) + ["k_flow"]:
+            for k in list(STEP_OF) + ["k_flow"] + list(GROUP_KERNELS):
                 if "nexg::" + k in name:
                     rows.setdefault(k, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     if "k_flow" in rows:
@@ -88,7 +123,7 @@ def steps_from(path, frames):
         sb = step_bytes(frames, buckets)
         total = {}
         for k, step in STEP_OF.items():
-            d = rows.get(k, [])
+            d = rows.get(k, [])[: 3 * len(BUCKETS)]  # a --groups run goes on to launch the scan kernels for the sort
             per = len(d) // len(BUCKETS)
             mine = d[bi * per: (bi + 1) * per]
             if not mine:
@@ -101,6 +136,21 @@ def steps_from(path, frames):
             print(json.dumps({"what": "partition step (trace)", "buckets": buckets, "step": step, "us": round(us, 2),
                               "bytes": sb[step], "tb_s": round(sb[step] / us / 1e6, 4),
                               "frac_of_8tb_s": round(sb[step] / us / 8e6, 4)}))
+    # a --quick --groups run: the sort's and the groups' own kernels; the groups' by flow population
+    # (one checking call and three timed ones each, in the order of the run)
+    for k in GROUP_KERNELS:
+        d = rows.get(k, [])
+        if not d:
+            continue
+        if k.startswith("k_sort"):
+            print(json.dumps({"what": k + " (trace)", "dispatches": len(d), "median_us": round(float(np.median(d)), 2),
+                              "sum_us_per_sort": round(float(np.median(d)) * 4, 2)}))
+            continue
+        per = len(d) // 3
+        for pi in range(3):
+            mine = d[pi * per: (pi + 1) * per]
+            print(json.dumps({"what": k + " (trace)", "population": pi, "dispatches": len(mine),
+                              "median_us": round(float(np.median(mine)), 2)}))
 
 
 def main():
@@ -109,6 +159,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--quick", action="store_true",
                     help="2 steps after 1 warm-up call, one repeat: the launches for a trace or counter pass, not a timing")
+    ap.add_argument("--groups", action="store_true",
+                    help="also time nexg_flow_sort and nexg_flow_groups (per-flow counters) on the same batch")
     ap.add_argument("--steps-from", metavar="CSV", help="summarise the partition kernels of a rocprofv3 kernel trace")
     args = ap.parse_args()
     if args.steps_from:
@@ -117,7 +169,7 @@ def main():
     import torch
     from nex_amd import abi
     from nex_amd.engine import Engine
-    from nex_amd.flow import FlowOption, flows_host, partition_host
+    from nex_amd.flow import FlowOption, flows_host, partition_host, sort_host
     if not torch.cuda.is_available():
         sys.exit("flow_rate needs the GPU: no rate is reported without one")
     eng = Engine(0)
@@ -192,7 +244,7 @@ def main():
             assert rc == abi.OK
 
         sb = step_bytes(n, buckets)
-        emit("flow_partition (count + scan + scatter)", part, 50, sum(sb.values()), buckets=buckets, workspace_bytes=wsb,
+        t = emit("flow_partition (count + scan + scatter)", part, 50, sum(sb.values()), buckets=buckets, workspace_bytes=wsb,
              step_bytes=sb)
         torch.cuda.synchronize()
         want_idx, want_first = partition_host(hf["hash"], buckets)
@@ -201,6 +253,62 @@ def main():
         sizes = np.diff(want_first)
         print(json.dumps({"what": "bucket sizes", "buckets": buckets, "min": int(sizes.min()), "max": int(sizes.max()),
                           "mean": round(float(sizes.mean()), 1)}), flush=True)
+        if buckets == 256:
+            t_part256 = t
+
+    if not args.groups:
+        return
+    # ---- per-flow counters: nexg_flow_sort, then nexg_flow_groups at three flow populations
+    order = torch.empty(n, dtype=torch.int32, device="cuda")
+    swb = abi.flow_sort_workspace(n)
+    sws = torch.empty(swb // 8, dtype=torch.int64, device="cuda")
+
+    def sort(rows=flows):
+        rc = lib.nexg_flow_sort(ctx, P(rows.data_ptr()), n, P(order.data_ptr()), P(sws.data_ptr()), swb, st)
+        assert rc == abi.OK
+
+    pb = sort_pass_bytes(n)
+    t_sort = emit("flow_sort (4 x (count + scan + scatter))", sort, 20, sum(sum(p.values()) for p in pb),
+                  workspace_bytes=swb, pass_bytes=pb)
+    torch.cuda.synchronize()
+    assert (order.cpu().numpy().view(np.uint32) == sort_host(hf["hash"])).all(), "flow_sort differs from sort_host"
+    print(json.dumps({"what": "flow_sort time / four flow_partition calls at 256 buckets",
+                      "ratio": round(t_sort / (4 * t_part256), 3)}), flush=True)
+
+    gwb = abi.flow_groups_workspace(n)
+    gws = torch.empty(gwb // 8, dtype=torch.int64, device="cuda")
+    rows_out = torch.empty(n * 32, dtype=torch.uint8, device="cuda")
+    group_of = torch.empty(n, dtype=torch.int32, device="cuda")
+    cnt = torch.zeros(1, dtype=torch.int64, device="cuda")
+    i64 = np.arange(n, dtype=np.uint64)
+    populations = [("the batch's own flows", flows)]
+    for pop in (1000, 1 << 20):
+        # the same records under made-up hashes: `pop` groups, their members dealt round-robin over the batch
+        rows = hf.copy()
+        rows["hash"] = ((i64 % np.uint64(pop)) * np.uint64(2654435761) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+        populations.append((f"{pop} made-up hashes over the same records", torch.from_numpy(rows.view(np.uint8)).cuda()))
+    for name, rows in populations:
+        sort(rows)
+
+        def groups():
+            rc = lib.nexg_flow_groups(ctx, ctypes.byref(fr), P(recs.data_ptr()), P(rows.data_ptr()), ctypes.byref(fo),
+                                      P(order.data_ptr()), P(rows_out.data_ptr()), n, P(group_of.data_ptr()),
+                                      P(cnt.data_ptr()), P(gws.data_ptr()), gwb, st)
+            assert rc == abi.OK
+
+        groups()
+        G = int(cnt.item())
+        hr = rows.cpu().numpy().view(abi.FLOW_DTYPE)
+        uniq, packets = np.unique(hr["hash"], return_counts=True)
+        got = rows_out.cpu().numpy().view(abi.FLOW_GROUP_DTYPE)[:G]
+        assert G == len(uniq) and (got["hash"] == uniq).all() and (got["packets"] == packets).all(), "flow_groups"
+        lens = np.diff(offs[: n + 1])
+        assert int(got["bytes"].sum()) == int(lens.sum()) and int(got["packets"].sum()) == n
+        gb = groups_step_bytes(n, G, v6_frames)
+        t = emit("flow_groups (mark + scans + place + rows)", groups, 20, sum(gb.values()), population=name, groups=G,
+                 mixed_groups=int((got["mixed"] != 0).sum()), workspace_bytes=gwb, step_bytes=gb)
+        print(json.dumps({"what": "flow_groups time / probe_stream time, per byte moved", "population": name,
+                          "ratio": round((t / sum(gb.values())) / (t_probe / (n * 72)), 3)}), flush=True)
 
 
 if __name__ == "__main__":
