@@ -110,6 +110,48 @@ nexg::ParseArgs to_args(const nexg_frames* f) {
     return a;
 }
 
+nexg::ParseArgs parse_args(const nexg_frames* f, const nexg_parse_option* option) {
+    nexg::ParseArgs a = to_args(f);
+    a.opt_flags = option ? option->flags : 0u;
+    a.ip_offset = option ? option->ip_offset : 0u;
+    return a;
+}
+
+// ---- what the entries' checks share; the texts stay each entry's own --------
+
+// one of the pointers has a bit of `mask` set (NULL is aligned)
+template <typename... P>
+bool misaligned(uint64_t mask, const P*... p) {
+    return ((reinterpret_cast<uint64_t>(p) | ...) & mask) != 0;
+}
+
+// the second passes number frames with 32 bits
+int check_count(nexg_ctx* ctx, const char* entry, uint64_t count) {
+    if (count <= 0xFFFFFFFFull) return NEXG_OK;
+    return fail(ctx, NEXG_EINVAL, "%s: more than 2^32 - 1 frames", entry);
+}
+
+// `have` bytes of workspace against `need`, what nexg_<entry>_workspace gives for `count`
+int check_workspace(nexg_ctx* ctx, const char* entry, uint64_t count, uint64_t have, uint64_t need) {
+    if (count == 0 || have >= need) return NEXG_OK;
+    return fail(ctx, NEXG_EINVAL, "%1$s: workspace smaller than nexg_%1$s_workspace", entry);  // the name twice
+}
+
+// nexg_flow_option as nexg_flow_batch and nexg_flow_groups take it (NULL: no flags)
+int flow_option_flags(nexg_ctx* ctx, const nexg_flow_option* option, uint32_t& flags) {
+    flags = 0u;
+    if (!option) return NEXG_OK;
+    if (option->reserved != 0) return fail(ctx, NEXG_EINVAL, "flow option: reserved must be 0%s", nullptr);
+    if ((option->flags & ~(NEXG_FLOW_SYMMETRIC | NEXG_FLOW_NO_PORTS | NEXG_FLOW_KEY)) != 0)
+        return fail(ctx, NEXG_EINVAL, "flow option: unknown flag bits%s", nullptr);
+    flags = option->flags;
+    return NEXG_OK;
+}
+
+// every entry's tail: the caller's stream handle, and the launch's error as a status
+hipStream_t as_stream(void* stream) { return static_cast<hipStream_t>(stream); }
+int launched(nexg_ctx* ctx, hipError_t e) { return hip_status(ctx, e, NEXG_ELAUNCH); }
+
 }  // namespace
 
 extern "C" {
@@ -170,24 +212,21 @@ int nexg_parse_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_parse_
     if (frames->count && !out) return fail(ctx, NEXG_EINVAL, "NULL output%s", nullptr);
     const uint64_t align_mask = out_kind == NEXG_OUT_VERDICT ? 1u : out_kind == NEXG_OUT_FLAGS ? 3u
                                 : out_kind == NEXG_OUT_DESC  ? 7u : 15u;
-    if ((reinterpret_cast<uint64_t>(out) & align_mask) != 0)
-        return fail(ctx, NEXG_EINVAL, "misaligned output%s", nullptr);
+    if (misaligned(align_mask, out)) return fail(ctx, NEXG_EINVAL, "misaligned output%s", nullptr);
     DeviceGuard g(ctx);
-    nexg::ParseArgs a = to_args(frames);
-    a.opt_flags = option ? option->flags : 0u;
-    a.ip_offset = option ? option->ip_offset : 0u;
+    nexg::ParseArgs a = parse_args(frames, option);
     a.out = out;
     a.tile_order = nexg::tile_order_for(a);
     const nexg::ParseVariant v = nexg::choose_parse_variant(a);
-    const hipStream_t st = static_cast<hipStream_t>(stream);
+    const hipStream_t st = as_stream(stream);
     if (nexg::parse_needs_tail(v, out_kind) && a.count) {
         a.tail = static_cast<uint32_t*>(scratch(ctx, a.count * 4u));
         if (!a.tail) return fail(ctx, NEXG_ENOMEM, "device scratch allocation failed%s", nullptr);
-        if (int rc = hip_status(ctx, scratch_acquire(ctx, st), NEXG_ELAUNCH)) return rc;
-        if (int rc = hip_status(ctx, nexg::launch_parse(v, a, out_kind, st), NEXG_ELAUNCH)) return rc;
-        return hip_status(ctx, scratch_release(ctx, st), NEXG_ELAUNCH);
+        if (int rc = launched(ctx, scratch_acquire(ctx, st))) return rc;
+        if (int rc = launched(ctx, nexg::launch_parse(v, a, out_kind, st))) return rc;
+        return launched(ctx, scratch_release(ctx, st));
     }
-    return hip_status(ctx, nexg::launch_parse(v, a, out_kind, st), NEXG_ELAUNCH);
+    return launched(ctx, nexg::launch_parse(v, a, out_kind, st));
 }
 
 static int sparse_expand(nexg_ctx* ctx, const nexg_frames* frames, const nexg_parse_option* option,
@@ -195,15 +234,12 @@ static int sparse_expand(nexg_ctx* ctx, const nexg_frames* frames, const nexg_pa
     if (!ctx) return NEXG_EINVAL;
     if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
     if (frames->count && (!sparse || !out)) return fail(ctx, NEXG_EINVAL, "NULL sparse input or output%s", nullptr);
-    if (((reinterpret_cast<uint64_t>(sparse) & 15u) | (reinterpret_cast<uint64_t>(out) & 7u)) != 0)
+    if (misaligned(15u, sparse) || misaligned(7u, out))
         return fail(ctx, NEXG_EINVAL, "misaligned sparse input or output%s", nullptr);
     DeviceGuard g(ctx);
-    nexg::ParseArgs a = to_args(frames);
-    a.opt_flags = option ? option->flags : 0u;
-    a.ip_offset = option ? option->ip_offset : 0u;
-    return hip_status(ctx, nexg::launch_sparse_expand(a, static_cast<const uint8_t*>(sparse), out, grouped,
-                                                      static_cast<hipStream_t>(stream)),
-                      NEXG_ELAUNCH);
+    const nexg::ParseArgs a = parse_args(frames, option);
+    return launched(ctx, nexg::launch_sparse_expand(a, static_cast<const uint8_t*>(sparse), out, grouped,
+                                                    as_stream(stream)));
 }
 
 int nexg_sparse_expand(nexg_ctx* ctx, const nexg_frames* frames, const nexg_parse_option* option,
@@ -221,12 +257,10 @@ int nexg_recompute_checksums_batch(nexg_ctx* ctx, const nexg_frames* frames, con
     if (!ctx) return NEXG_EINVAL;
     if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
     if ((which & ~(NEXG_FIX_IP | NEXG_FIX_L4)) != 0) return fail(ctx, NEXG_EINVAL, "invalid fix-up selection%s", nullptr);
-    if ((reinterpret_cast<uint64_t>(out) & 7u) != 0) return fail(ctx, NEXG_EINVAL, "misaligned output%s", nullptr);
+    if (misaligned(7u, out)) return fail(ctx, NEXG_EINVAL, "misaligned output%s", nullptr);
     DeviceGuard g(ctx);
-    nexg::ParseArgs a = to_args(frames);
-    a.opt_flags = option ? option->flags : 0u;
-    a.ip_offset = option ? option->ip_offset : 0u;
-    return hip_status(ctx, nexg::launch_recompute(a, which, out, static_cast<hipStream_t>(stream)), NEXG_ELAUNCH);
+    const nexg::ParseArgs a = parse_args(frames, option);
+    return launched(ctx, nexg::launch_recompute(a, which, out, as_stream(stream)));
 }
 
 int nexg_checksum_batch(nexg_ctx* ctx, const nexg_frames* bufs, uint32_t skipword, uint16_t* out,
@@ -236,8 +270,7 @@ int nexg_checksum_batch(nexg_ctx* ctx, const nexg_frames* bufs, uint32_t skipwor
     if (bufs->count && !out) return fail(ctx, NEXG_EINVAL, "NULL output%s", nullptr);
     nexg::ParseArgs a = to_args(bufs);
     DeviceGuard g(ctx);
-    return hip_status(ctx, nexg::launch_checksum(a, skipword, out, static_cast<hipStream_t>(stream)),
-                      NEXG_ELAUNCH);
+    return launched(ctx, nexg::launch_checksum(a, skipword, out, as_stream(stream)));
 }
 
 int nexg_decode_options(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records,
@@ -245,12 +278,10 @@ int nexg_decode_options(nexg_ctx* ctx, const nexg_frames* frames, const nexg_rec
     if (!ctx) return NEXG_EINVAL;
     if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
     if (frames->count && (!records || !out)) return fail(ctx, NEXG_EINVAL, "NULL records or output%s", nullptr);
-    if ((reinterpret_cast<uint64_t>(out) & 15u) != 0 || (reinterpret_cast<uint64_t>(records) & 15u) != 0)
-        return fail(ctx, NEXG_EINVAL, "misaligned records or output%s", nullptr);
+    if (misaligned(15u, records, out)) return fail(ctx, NEXG_EINVAL, "misaligned records or output%s", nullptr);
     const nexg::ParseArgs a = to_args(frames);
     DeviceGuard g(ctx);
-    return hip_status(ctx, nexg::launch_decode_options(a, records, out, static_cast<hipStream_t>(stream)),
-                      NEXG_ELAUNCH);
+    return launched(ctx, nexg::launch_decode_options(a, records, out, as_stream(stream)));
 }
 
 int nexg_decap_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records,
@@ -268,14 +299,11 @@ int nexg_decap_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record
     }
     if (frames->count && (!records || !tunnels || !inner_off || !inner_len))
         return fail(ctx, NEXG_EINVAL, "NULL records or output%s", nullptr);
-    if ((reinterpret_cast<uint64_t>(records) & 15u) != 0 || (reinterpret_cast<uint64_t>(tunnels) & 15u) != 0 ||
-        (reinterpret_cast<uint64_t>(inner_off) & 7u) != 0 || (reinterpret_cast<uint64_t>(inner_len) & 3u) != 0)
+    if (misaligned(15u, records, tunnels) || misaligned(7u, inner_off) || misaligned(3u, inner_len))
         return fail(ctx, NEXG_EINVAL, "misaligned records or output%s", nullptr);
     const nexg::ParseArgs a = to_args(frames);
     DeviceGuard g(ctx);
-    return hip_status(ctx, nexg::launch_decap(a, records, which, port, tunnels, inner_off, inner_len,
-                                              static_cast<hipStream_t>(stream)),
-                      NEXG_ELAUNCH);
+    return launched(ctx, nexg::launch_decap(a, records, which, port, tunnels, inner_off, inner_len, as_stream(stream)));
 }
 
 int nexg_decap_select(nexg_ctx* ctx, const nexg_tunnel* tunnels, const uint64_t* inner_off,
@@ -283,23 +311,19 @@ int nexg_decap_select(nexg_ctx* ctx, const nexg_tunnel* tunnels, const uint64_t*
                       uint64_t* out_off, uint32_t* out_len, uint64_t* out_count, void* workspace,
                       uint64_t workspace_bytes, void* stream) {
     if (!ctx) return NEXG_EINVAL;
-    if (count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "decap_select: more than 2^32 - 1 frames%s", nullptr);
+    if (int rc = check_count(ctx, "decap_select", count)) return rc;
     if (!out_count) return fail(ctx, NEXG_EINVAL, "NULL out_count%s", nullptr);
     if (count && (!tunnels || !inner_off || !inner_len || !out_index || !out_off || !out_len || !workspace))
         return fail(ctx, NEXG_EINVAL, "NULL input, output or workspace%s", nullptr);
-    if (count && workspace_bytes < nexg_decap_select_workspace(count))
-        return fail(ctx, NEXG_EINVAL, "decap_select: workspace smaller than nexg_decap_select_workspace%s", nullptr);
-    if ((reinterpret_cast<uint64_t>(tunnels) & 15u) != 0 ||
-        ((reinterpret_cast<uint64_t>(inner_off) | reinterpret_cast<uint64_t>(out_off) |
-          reinterpret_cast<uint64_t>(out_count)) & 7u) != 0 ||
-        ((reinterpret_cast<uint64_t>(inner_len) | reinterpret_cast<uint64_t>(out_index) |
-          reinterpret_cast<uint64_t>(out_len) | reinterpret_cast<uint64_t>(workspace)) & 3u) != 0)
+    if (int rc = check_workspace(ctx, "decap_select", count, workspace_bytes, nexg_decap_select_workspace(count)))
+        return rc;
+    if (misaligned(15u, tunnels) || misaligned(7u, inner_off, out_off, out_count) ||
+        misaligned(3u, inner_len, out_index, out_len, workspace))
         return fail(ctx, NEXG_EINVAL, "misaligned input, output or workspace%s", nullptr);
     DeviceGuard g(ctx);
-    return hip_status(ctx, nexg::launch_decap_select(tunnels, inner_off, inner_len, count, inner_mask, out_index,
-                                                     out_off, out_len, out_count, static_cast<uint32_t*>(workspace),
-                                                     static_cast<hipStream_t>(stream)),
-                      NEXG_ELAUNCH);
+    return launched(ctx, nexg::launch_decap_select(tunnels, inner_off, inner_len, count, inner_mask, out_index, out_off,
+                                                   out_len, out_count, static_cast<uint32_t*>(workspace),
+                                                   as_stream(stream)));
 }
 
 int nexg_dns_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records,
@@ -314,36 +338,30 @@ int nexg_dns_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* 
         flags = option->flags;
         if (option->port) port = option->port;
     }
-    if (frames->count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "dns: more than 2^32 - 1 frames%s", nullptr);
+    if (int rc = check_count(ctx, "dns", frames->count)) return rc;
     if (frames->count && (!records || !out || !tile_first))
         return fail(ctx, NEXG_EINVAL, "NULL records or output%s", nullptr);
-    if (((reinterpret_cast<uint64_t>(records) | reinterpret_cast<uint64_t>(out)) & 15u) != 0 ||
-        (reinterpret_cast<uint64_t>(tile_first) & 7u) != 0)
+    if (misaligned(15u, records, out) || misaligned(7u, tile_first))
         return fail(ctx, NEXG_EINVAL, "misaligned records or output%s", nullptr);
     if (!tile_first) return NEXG_OK;  // an empty batch with nowhere to put its total
     const nexg::ParseArgs a = to_args(frames);
     DeviceGuard g(ctx);
-    return hip_status(ctx, nexg::launch_dns(a, records, flags & NEXG_DNS_ANY_UDP, port, out, tile_first,
-                                            static_cast<hipStream_t>(stream)),
-                      NEXG_ELAUNCH);
+    return launched(ctx, nexg::launch_dns(a, records, flags & NEXG_DNS_ANY_UDP, port, out, tile_first, as_stream(stream)));
 }
 
 int nexg_dns_entries(nexg_ctx* ctx, const nexg_frames* frames, const nexg_dns* dns, const uint64_t* tile_first,
                      nexg_dns_entry* entries, uint64_t entries_cap, void* stream) {
     if (!ctx) return NEXG_EINVAL;
     if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
-    if (frames->count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "dns: more than 2^32 - 1 frames%s", nullptr);
+    if (int rc = check_count(ctx, "dns", frames->count)) return rc;
     if (frames->count && (!dns || !tile_first)) return fail(ctx, NEXG_EINVAL, "NULL summaries or tile_first%s", nullptr);
     if (entries_cap && !entries) return fail(ctx, NEXG_EINVAL, "NULL entries with a nonzero capacity%s", nullptr);
-    if (((reinterpret_cast<uint64_t>(dns) | reinterpret_cast<uint64_t>(entries)) & 15u) != 0 ||
-        (reinterpret_cast<uint64_t>(tile_first) & 7u) != 0)
+    if (misaligned(15u, dns, entries) || misaligned(7u, tile_first))
         return fail(ctx, NEXG_EINVAL, "misaligned summaries, tile_first or entries%s", nullptr);
     if (!entries) return NEXG_OK;  // capacity 0: nothing to store
     const nexg::ParseArgs a = to_args(frames);
     DeviceGuard g(ctx);
-    return hip_status(ctx, nexg::launch_dns_entries(a, dns, tile_first, entries, entries_cap,
-                                                    static_cast<hipStream_t>(stream)),
-                      NEXG_ELAUNCH);
+    return launched(ctx, nexg::launch_dns_entries(a, dns, tile_first, entries, entries_cap, as_stream(stream)));
 }
 
 int nexg_filter_check(const nexg_filter* filter) {
@@ -359,22 +377,17 @@ int nexg_select_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_recor
     nexg::SelFilter f;
     if (const char* why = nexg::prepare_filter(filter, &f)) return fail(ctx, NEXG_EINVAL, "select: %s", why);
     const uint64_t count = frames->count;
-    if (count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "select: more than 2^32 - 1 frames%s", nullptr);
+    if (int rc = check_count(ctx, "select", count)) return rc;
     if (!out_count) return fail(ctx, NEXG_EINVAL, "NULL out_count%s", nullptr);
     if (count && (!records || !out_index || !out_off || !out_len || !workspace))
         return fail(ctx, NEXG_EINVAL, "NULL records, output or workspace%s", nullptr);
-    if (count && workspace_bytes < nexg_select_workspace(count))
-        return fail(ctx, NEXG_EINVAL, "select: workspace smaller than nexg_select_workspace%s", nullptr);
-    if ((reinterpret_cast<uint64_t>(records) & 15u) != 0 ||
-        ((reinterpret_cast<uint64_t>(out_off) | reinterpret_cast<uint64_t>(out_count)) & 7u) != 0 ||
-        ((reinterpret_cast<uint64_t>(out_index) | reinterpret_cast<uint64_t>(out_len) |
-          reinterpret_cast<uint64_t>(workspace)) & 3u) != 0)
+    if (int rc = check_workspace(ctx, "select", count, workspace_bytes, nexg_select_workspace(count))) return rc;
+    if (misaligned(15u, records) || misaligned(7u, out_off, out_count) || misaligned(3u, out_index, out_len, workspace))
         return fail(ctx, NEXG_EINVAL, "misaligned records, output or workspace%s", nullptr);
     const nexg::ParseArgs a = to_args(frames);
     DeviceGuard g(ctx);
-    return hip_status(ctx, nexg::launch_select(a, records, f, out_index, out_off, out_len, out_rule, out_count,
-                                               static_cast<uint32_t*>(workspace), static_cast<hipStream_t>(stream)),
-                      NEXG_ELAUNCH);
+    return launched(ctx, nexg::launch_select(a, records, f, out_index, out_off, out_len, out_rule, out_count,
+                                             static_cast<uint32_t*>(workspace), as_stream(stream)));
 }
 
 int nexg_gather_plan(nexg_ctx* ctx, const nexg_frames* sel, uint32_t align, uint64_t* out_offsets,
@@ -384,35 +397,30 @@ int nexg_gather_plan(nexg_ctx* ctx, const nexg_frames* sel, uint32_t align, uint
     if (align != 1 && align != 4 && align != 8 && align != 16)
         return fail(ctx, NEXG_EINVAL, "gather_plan: align must be 1, 4, 8 or 16%s", nullptr);
     const uint64_t count = sel->count;
-    if (count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "gather_plan: more than 2^32 - 1 frames%s", nullptr);
+    if (int rc = check_count(ctx, "gather_plan", count)) return rc;
     if (!out_offsets) return fail(ctx, NEXG_EINVAL, "NULL out_offsets%s", nullptr);
     if (count && !workspace) return fail(ctx, NEXG_EINVAL, "NULL workspace%s", nullptr);
-    if (count && workspace_bytes < nexg_gather_plan_workspace(count))
-        return fail(ctx, NEXG_EINVAL, "gather_plan: workspace smaller than nexg_gather_plan_workspace%s", nullptr);
-    if (((reinterpret_cast<uint64_t>(out_offsets) | reinterpret_cast<uint64_t>(workspace)) & 7u) != 0 ||
-        (reinterpret_cast<uint64_t>(out_len) & 3u) != 0)
+    if (int rc = check_workspace(ctx, "gather_plan", count, workspace_bytes, nexg_gather_plan_workspace(count))) return rc;
+    if (misaligned(7u, out_offsets, workspace) || misaligned(3u, out_len))
         return fail(ctx, NEXG_EINVAL, "misaligned output or workspace%s", nullptr);
     const nexg::ParseArgs a = to_args(sel);
     DeviceGuard g(ctx);
-    return hip_status(ctx, nexg::launch_gather_plan(a, align, out_offsets, out_len, static_cast<uint64_t*>(workspace),
-                                                    static_cast<hipStream_t>(stream)),
-                      NEXG_ELAUNCH);
+    return launched(ctx, nexg::launch_gather_plan(a, align, out_offsets, out_len, static_cast<uint64_t*>(workspace),
+                                                  as_stream(stream)));
 }
 
 int nexg_gather_frames(nexg_ctx* ctx, const nexg_frames* sel, const uint64_t* out_offsets, uint8_t* out_data,
                        uint64_t out_cap, void* stream) {
     if (!ctx) return NEXG_EINVAL;
     if (!frames_valid(sel)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
-    if (sel->count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "gather_frames: more than 2^32 - 1 frames%s", nullptr);
+    if (int rc = check_count(ctx, "gather_frames", sel->count)) return rc;
     if (sel->count && !out_offsets) return fail(ctx, NEXG_EINVAL, "NULL out_offsets%s", nullptr);
     if (out_cap && !out_data) return fail(ctx, NEXG_EINVAL, "NULL out_data with a nonzero capacity%s", nullptr);
-    if ((reinterpret_cast<uint64_t>(out_offsets) & 7u) != 0 || (reinterpret_cast<uint64_t>(out_data) & 15u) != 0)
+    if (misaligned(7u, out_offsets) || misaligned(15u, out_data))
         return fail(ctx, NEXG_EINVAL, "misaligned out_offsets or out_data%s", nullptr);
     const nexg::ParseArgs a = to_args(sel);
     DeviceGuard g(ctx);
-    return hip_status(ctx, nexg::launch_gather_frames(a, out_offsets, out_data, out_cap,
-                                                      static_cast<hipStream_t>(stream)),
-                      NEXG_ELAUNCH);
+    return launched(ctx, nexg::launch_gather_frames(a, out_offsets, out_data, out_cap, as_stream(stream)));
 }
 
 int nexg_gather_rows(nexg_ctx* ctx, const void* rows, uint32_t row_bytes, uint64_t rows_count,
@@ -424,13 +432,10 @@ int nexg_gather_rows(nexg_ctx* ctx, const void* rows, uint32_t row_bytes, uint64
     if (n && (!index || !out || (rows_count && !rows)))
         return fail(ctx, NEXG_EINVAL, "NULL rows, index or output%s", nullptr);
     const uint64_t am = (row_bytes < 16u ? row_bytes : 16u) - 1u;
-    if (((reinterpret_cast<uint64_t>(rows) | reinterpret_cast<uint64_t>(out)) & am) != 0 ||
-        (reinterpret_cast<uint64_t>(index) & 3u) != 0)
+    if (misaligned(am, rows, out) || misaligned(3u, index))
         return fail(ctx, NEXG_EINVAL, "misaligned rows, index or output%s", nullptr);
     DeviceGuard g(ctx);
-    return hip_status(ctx, nexg::launch_gather_rows(rows, row_bytes, rows_count, index, n, out,
-                                                    static_cast<hipStream_t>(stream)),
-                      NEXG_ELAUNCH);
+    return launched(ctx, nexg::launch_gather_rows(rows, row_bytes, rows_count, index, n, out, as_stream(stream)));
 }
 
 int nexg_flow_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records,
@@ -438,17 +443,11 @@ int nexg_flow_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record*
     static const uint8_t default_key[40] = NEXG_FLOW_DEFAULT_KEY;
     if (!ctx) return NEXG_EINVAL;
     if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
-    uint32_t flags = 0u;
-    const uint8_t* key = default_key;
-    if (option) {
-        if (option->reserved != 0) return fail(ctx, NEXG_EINVAL, "flow option: reserved must be 0%s", nullptr);
-        if ((option->flags & ~(NEXG_FLOW_SYMMETRIC | NEXG_FLOW_NO_PORTS | NEXG_FLOW_KEY)) != 0)
-            return fail(ctx, NEXG_EINVAL, "flow option: unknown flag bits%s", nullptr);
-        flags = option->flags;
-        if (flags & NEXG_FLOW_KEY) key = option->key;
-    }
+    uint32_t flags;
+    if (int rc = flow_option_flags(ctx, option, flags)) return rc;
+    const uint8_t* key = (flags & NEXG_FLOW_KEY) ? option->key : default_key;
     if (frames->count && (!records || !out)) return fail(ctx, NEXG_EINVAL, "NULL records or output%s", nullptr);
-    if ((reinterpret_cast<uint64_t>(records) & 15u) != 0 || (reinterpret_cast<uint64_t>(out) & 7u) != 0)
+    if (misaligned(15u, records) || misaligned(7u, out))
         return fail(ctx, NEXG_EINVAL, "misaligned records or output%s", nullptr);
     nexg::FlowKey k;
     for (uint32_t i = 0; i < 10; i++)
@@ -456,7 +455,7 @@ int nexg_flow_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record*
                  (uint32_t)key[4 * i + 3];
     const nexg::ParseArgs a = to_args(frames);
     DeviceGuard g(ctx);
-    return hip_status(ctx, nexg::launch_flow(a, records, flags, k, out, static_cast<hipStream_t>(stream)), NEXG_ELAUNCH);
+    return launched(ctx, nexg::launch_flow(a, records, flags, k, out, as_stream(stream)));
 }
 
 int nexg_flow_partition(nexg_ctx* ctx, const nexg_frames* frames, const nexg_flow* flows, uint32_t buckets,
@@ -466,39 +465,33 @@ int nexg_flow_partition(nexg_ctx* ctx, const nexg_frames* frames, const nexg_flo
     if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
     if (buckets < 1u || buckets > 256u) return fail(ctx, NEXG_EINVAL, "flow_partition: buckets must be 1..256%s", nullptr);
     const uint64_t count = frames->count;
-    if (count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "flow_partition: more than 2^32 - 1 frames%s", nullptr);
+    if (int rc = check_count(ctx, "flow_partition", count)) return rc;
     if (!bucket_first) return fail(ctx, NEXG_EINVAL, "NULL bucket_first%s", nullptr);
     if ((out_off == nullptr) != (out_len == nullptr))
         return fail(ctx, NEXG_EINVAL, "flow_partition: out_off and out_len go together%s", nullptr);
     if (count && (!flows || !out_index || !workspace))
         return fail(ctx, NEXG_EINVAL, "NULL flows, output or workspace%s", nullptr);
-    if (count && workspace_bytes < nexg_flow_partition_workspace(count, buckets))
-        return fail(ctx, NEXG_EINVAL, "flow_partition: workspace smaller than nexg_flow_partition_workspace%s", nullptr);
-    if (((reinterpret_cast<uint64_t>(flows) | reinterpret_cast<uint64_t>(out_off) |
-          reinterpret_cast<uint64_t>(bucket_first) | reinterpret_cast<uint64_t>(workspace)) & 7u) != 0 ||
-        ((reinterpret_cast<uint64_t>(out_index) | reinterpret_cast<uint64_t>(out_len)) & 3u) != 0)
+    const uint64_t need = nexg_flow_partition_workspace(count, buckets);
+    if (int rc = check_workspace(ctx, "flow_partition", count, workspace_bytes, need)) return rc;
+    if (misaligned(7u, flows, out_off, bucket_first, workspace) || misaligned(3u, out_index, out_len))
         return fail(ctx, NEXG_EINVAL, "misaligned flows, output or workspace%s", nullptr);
     const nexg::ParseArgs a = to_args(frames);
     DeviceGuard g(ctx);
-    return hip_status(ctx, nexg::launch_flow_partition(a, flows, buckets, out_index, out_off, out_len, bucket_first,
-                                                       workspace, static_cast<hipStream_t>(stream)),
-                      NEXG_ELAUNCH);
+    return launched(ctx, nexg::launch_flow_partition(a, flows, buckets, out_index, out_off, out_len, bucket_first,
+                                                     workspace, as_stream(stream)));
 }
 
 int nexg_flow_sort(nexg_ctx* ctx, const nexg_flow* flows, uint64_t count, uint32_t* out_index, void* workspace,
                    uint64_t workspace_bytes, void* stream) {
     if (!ctx) return NEXG_EINVAL;
-    if (count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "flow_sort: more than 2^32 - 1 frames%s", nullptr);
+    if (int rc = check_count(ctx, "flow_sort", count)) return rc;
     if (count && (!flows || !out_index || !workspace))
         return fail(ctx, NEXG_EINVAL, "NULL flows, output or workspace%s", nullptr);
-    if (count && workspace_bytes < nexg_flow_sort_workspace(count))
-        return fail(ctx, NEXG_EINVAL, "flow_sort: workspace smaller than nexg_flow_sort_workspace%s", nullptr);
-    if (((reinterpret_cast<uint64_t>(flows) | reinterpret_cast<uint64_t>(workspace)) & 7u) != 0 ||
-        (reinterpret_cast<uint64_t>(out_index) & 3u) != 0)
+    if (int rc = check_workspace(ctx, "flow_sort", count, workspace_bytes, nexg_flow_sort_workspace(count))) return rc;
+    if (misaligned(7u, flows, workspace) || misaligned(3u, out_index))
         return fail(ctx, NEXG_EINVAL, "misaligned flows, output or workspace%s", nullptr);
     DeviceGuard g(ctx);
-    return hip_status(ctx, nexg::launch_flow_sort(flows, count, out_index, workspace, static_cast<hipStream_t>(stream)),
-                      NEXG_ELAUNCH);
+    return launched(ctx, nexg::launch_flow_sort(flows, count, out_index, workspace, as_stream(stream)));
 }
 
 int nexg_flow_groups(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records, const nexg_flow* flows,
@@ -506,30 +499,20 @@ int nexg_flow_groups(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record
                      uint32_t* out_group, uint64_t* out_count, void* workspace, uint64_t workspace_bytes, void* stream) {
     if (!ctx) return NEXG_EINVAL;
     if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
-    uint32_t flags = 0u;
-    if (option) {
-        if (option->reserved != 0) return fail(ctx, NEXG_EINVAL, "flow option: reserved must be 0%s", nullptr);
-        if ((option->flags & ~(NEXG_FLOW_SYMMETRIC | NEXG_FLOW_NO_PORTS | NEXG_FLOW_KEY)) != 0)
-            return fail(ctx, NEXG_EINVAL, "flow option: unknown flag bits%s", nullptr);
-        flags = option->flags;
-    }
+    uint32_t flags;
+    if (int rc = flow_option_flags(ctx, option, flags)) return rc;
     const uint64_t count = frames->count;
-    if (count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "flow_groups: more than 2^32 - 1 frames%s", nullptr);
+    if (int rc = check_count(ctx, "flow_groups", count)) return rc;
     if (!out_count) return fail(ctx, NEXG_EINVAL, "NULL out_count%s", nullptr);
     if (count && (!records || !flows || !order || !workspace || (groups_cap && !out)))
         return fail(ctx, NEXG_EINVAL, "NULL records, flows, order, output or workspace%s", nullptr);
-    if (count && workspace_bytes < nexg_flow_groups_workspace(count))
-        return fail(ctx, NEXG_EINVAL, "flow_groups: workspace smaller than nexg_flow_groups_workspace%s", nullptr);
-    if (((reinterpret_cast<uint64_t>(records) | reinterpret_cast<uint64_t>(out)) & 15u) != 0 ||
-        ((reinterpret_cast<uint64_t>(flows) | reinterpret_cast<uint64_t>(out_count) |
-          reinterpret_cast<uint64_t>(workspace)) & 7u) != 0 ||
-        ((reinterpret_cast<uint64_t>(order) | reinterpret_cast<uint64_t>(out_group)) & 3u) != 0)
+    if (int rc = check_workspace(ctx, "flow_groups", count, workspace_bytes, nexg_flow_groups_workspace(count))) return rc;
+    if (misaligned(15u, records, out) || misaligned(7u, flows, out_count, workspace) || misaligned(3u, order, out_group))
         return fail(ctx, NEXG_EINVAL, "misaligned records, flows, order, output or workspace%s", nullptr);
     const nexg::ParseArgs a = to_args(frames);
     DeviceGuard g(ctx);
-    return hip_status(ctx, nexg::launch_flow_groups(a, records, flows, flags, order, out, groups_cap, out_group, out_count,
-                                                    workspace, static_cast<hipStream_t>(stream)),
-                      NEXG_ELAUNCH);
+    return launched(ctx, nexg::launch_flow_groups(a, records, flows, flags, order, out, groups_cap, out_group, out_count,
+                                                  workspace, as_stream(stream)));
 }
 
 int nexg_probe_stream(nexg_ctx* ctx, const void* data, uint64_t bytes, uint32_t out_per_64,
@@ -552,18 +535,16 @@ int nexg_probe_span_clock(nexg_ctx* ctx, const nexg_frames* frames, const nexg_p
     if (!ctx) return NEXG_EINVAL;
     if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
     if (frames->count && (!out || !stamps)) return fail(ctx, NEXG_EINVAL, "NULL output or stamps%s", nullptr);
-    if (((reinterpret_cast<uint64_t>(out) & 15u) | (reinterpret_cast<uint64_t>(stamps) & 7u)) != 0)
+    if (misaligned(15u, out) || misaligned(7u, stamps))
         return fail(ctx, NEXG_EINVAL, "misaligned output or stamps%s", nullptr);
     DeviceGuard g(ctx);
-    nexg::ParseArgs a = to_args(frames);
-    a.opt_flags = option ? option->flags : 0u;
-    a.ip_offset = option ? option->ip_offset : 0u;
+    nexg::ParseArgs a = parse_args(frames, option);
     a.out = out;
     a.tile_order = nexg::tile_order_for(a);
     a.stamps = stamps;
     if (nexg::choose_parse_variant(a) != nexg::ParseVariant::SpanTile)
         return fail(ctx, NEXG_EINVAL, "probe_span_clock: the batch does not take the span kernel%s", nullptr);
-    return hip_status(ctx, nexg::launch_span_clock(a, static_cast<hipStream_t>(stream)), NEXG_ELAUNCH);
+    return launched(ctx, nexg::launch_span_clock(a, as_stream(stream)));
 }
 
 int nexg_probe_latency(nexg_ctx* ctx, void* buf, uint64_t bytes, uint32_t steps, uint32_t start, uint32_t loaded,

@@ -9,6 +9,7 @@
 // stable LSD radix sort of (hash, index) pairs), and nexg_flow_groups reduces
 // the sorted batch to one row per run of equal hashes by prefix sums.
 #include "table_kernels.hpp"
+#include "workspace_layout.hpp"
 
 namespace nexg {
 
@@ -155,6 +156,7 @@ constexpr uint32_t kPartTile = NEXG_FLOW_TILE;  // frames per workgroup: each of
 constexpr uint32_t kPartRounds = kPartTile / kTile;  // frames and takes them 64 at a time
 constexpr uint32_t kScanChunk = 1024;
 static_assert(kPartTile == 4u * 64u * kPartRounds, "four waves, whole rounds");
+static_assert(kScanChunk == FlowPartLayout::kChunk, "the workspace holds one sum per chunk of the scan");
 
 // the lanes of the wave whose frame is valid and falls into this lane's bucket:
 // one ballot per bucket bit
@@ -244,6 +246,15 @@ __global__ __launch_bounds__(256) void k_chunk_apply(uint32_t* v, uint64_t n, co
         carry += total;
         __syncthreads();  // s_w is rewritten by the next step
     }
+}
+
+// the scan's three kernels over the n counters of `hist`, in place
+static void launch_counter_scan(uint32_t* hist, uint64_t n, uint32_t* sums, uint64_t* total, hipStream_t s) {
+    const uint64_t chunks = (n + kScanChunk - 1) / kScanChunk;
+    const dim3 gC((uint32_t)chunks), b(kTile);
+    hipLaunchKernelGGL(k_chunk_sums, gC, b, 0, s, hist, n, sums);
+    hipLaunchKernelGGL(k_tile_scan<uint32_t>, dim3(1), b, 0, s, sums, chunks, total);
+    hipLaunchKernelGGL(k_chunk_apply, gC, b, 0, s, hist, n, sums);
 }
 
 // k_part_scatter: phase A again (the histogram of each wave's 256 frames), then
@@ -343,17 +354,12 @@ hipError_t launch_flow_partition(const ParseArgs& a, const nexg_flow* flows, uin
                                  uint64_t* out_off, uint32_t* out_len, uint64_t* bucket_first, void* workspace,
                                  hipStream_t s) {
     if (a.count == 0) return hipMemsetAsync(bucket_first, 0, 8u * ((uint64_t)buckets + 1u), s);
-    const uint64_t T = (a.count + kPartTile - 1) / kPartTile, n = T * buckets;
-    const uint64_t chunks = (n + kScanChunk - 1) / kScanChunk;
-    // the workspace as nexg_flow_partition_workspace lays it out
-    uint64_t* total = static_cast<uint64_t*>(workspace);
-    uint32_t* sums = reinterpret_cast<uint32_t*>(total + 1);
-    uint32_t* hist = sums + ((chunks + 1u) & ~1ull);
+    const FlowPartLayout w = FlowPartLayout::from(a.count, buckets);
+    const uint64_t T = w.tiles;
+    uint32_t* hist = region<uint32_t>(workspace, w.hist);
     const uint32_t nbits = buckets > 1u ? 32u - (uint32_t)__builtin_clz(buckets - 1u) : 0u;
     hipLaunchKernelGGL(k_part_count, dim3((uint32_t)T), dim3(kTile), 0, s, flows, a.count, buckets, nbits, T, hist);
-    hipLaunchKernelGGL(k_chunk_sums, dim3((uint32_t)chunks), dim3(kTile), 0, s, hist, n, sums);
-    hipLaunchKernelGGL(k_tile_scan<uint32_t>, dim3(1), dim3(kTile), 0, s, sums, chunks, total);
-    hipLaunchKernelGGL(k_chunk_apply, dim3((uint32_t)chunks), dim3(kTile), 0, s, hist, n, sums);
+    launch_counter_scan(hist, w.counters, region<uint32_t>(workspace, w.sums), region<uint64_t>(workspace, w.total), s);
     hipLaunchKernelGGL(k_part_scatter, dim3((uint32_t)T), dim3(kTile), 0, s, a, flows, buckets, nbits, T, hist, out_index,
                        out_off, out_len, bucket_first);
     return hipGetLastError();
@@ -428,15 +434,12 @@ __global__ __launch_bounds__(256) void k_sort_scatter(const void* src, uint64_t 
 
 hipError_t launch_flow_sort(const nexg_flow* flows, uint64_t count, uint32_t* out_index, void* workspace, hipStream_t s) {
     if (count == 0) return hipSuccess;
-    const uint64_t T = (count + kPartTile - 1) / kPartTile, n = T * 256u;
-    const uint64_t chunks = (n + kScanChunk - 1) / kScanChunk;
-    // the workspace as nexg_flow_sort_workspace lays it out
-    uint64_t* total = static_cast<uint64_t*>(workspace);
-    uint32_t* sums = reinterpret_cast<uint32_t*>(total + 1);
-    uint32_t* hist = sums + ((chunks + 1u) & ~1ull);
-    uint64_t* ping = reinterpret_cast<uint64_t*>(hist + n);
-    uint64_t* pong = ping + count;
-    const dim3 gT((uint32_t)T), gC((uint32_t)chunks), b(kTile);
+    const FlowSortLayout w = FlowSortLayout::from(count);
+    const uint64_t T = w.tiles;
+    uint32_t* hist = region<uint32_t>(workspace, w.hist);
+    uint64_t* ping = region<uint64_t>(workspace, w.ping);
+    uint64_t* pong = region<uint64_t>(workspace, w.pong);
+    const dim3 gT((uint32_t)T), b(kTile);
     for (uint32_t pass = 0; pass < 4; pass++) {
         const void* src = pass == 0 ? static_cast<const void*>(flows) : (pass & 1u) ? ping : pong;
         uint64_t* dst = (pass & 1u) ? pong : ping;
@@ -445,9 +448,7 @@ hipError_t launch_flow_sort(const nexg_flow* flows, uint64_t count, uint32_t* ou
             hipLaunchKernelGGL(k_sort_count<true>, gT, b, 0, s, src, count, shift, T, hist);
         else
             hipLaunchKernelGGL(k_sort_count<false>, gT, b, 0, s, src, count, shift, T, hist);
-        hipLaunchKernelGGL(k_chunk_sums, gC, b, 0, s, hist, n, sums);
-        hipLaunchKernelGGL(k_tile_scan<uint32_t>, dim3(1), b, 0, s, sums, chunks, total);
-        hipLaunchKernelGGL(k_chunk_apply, gC, b, 0, s, hist, n, sums);
+        launch_counter_scan(hist, w.counters, region<uint32_t>(workspace, w.sums), region<uint64_t>(workspace, w.total), s);
         if (pass == 0)
             hipLaunchKernelGGL((k_sort_scatter<true, false>), gT, b, 0, s, src, count, shift, T, hist, dst, out_index);
         else if (pass < 3)
@@ -570,14 +571,14 @@ hipError_t launch_flow_groups(const ParseArgs& a, const nexg_record* recs, const
                               uint64_t* out_count, void* workspace, hipStream_t s) {
     const uint64_t count = a.count;
     if (count == 0) return hipMemsetAsync(out_count, 0, 8, s);
-    const uint64_t tiles = (count + kTile - 1) / kTile, tp = (tiles + 1u) & ~1ull;
-    // the workspace as nexg_flow_groups_workspace lays it out
-    uint64_t* totals = static_cast<uint64_t*>(workspace);  // breaks, bytes
-    uint64_t* tile_bytes = totals + 2;
-    uint64_t* mark = tile_bytes + tiles;
-    uint32_t* tile_heads = reinterpret_cast<uint32_t*>(mark + count);
-    uint32_t* tile_brk = tile_heads + tp;
-    uint32_t* starts = tile_brk + tp;
+    const FlowGroupsLayout w = FlowGroupsLayout::from(count);
+    const uint64_t tiles = w.tiles;
+    uint64_t* totals = region<uint64_t>(workspace, w.totals);  // breaks, bytes
+    uint64_t* tile_bytes = region<uint64_t>(workspace, w.tile_bytes);
+    uint64_t* mark = region<uint64_t>(workspace, w.mark);
+    uint32_t* tile_heads = region<uint32_t>(workspace, w.tile_heads);
+    uint32_t* tile_brk = region<uint32_t>(workspace, w.tile_brk);
+    uint32_t* starts = region<uint32_t>(workspace, w.starts);
     const dim3 gT((uint32_t)tiles), b(kTile);
     hipLaunchKernelGGL(k_group_mark, gT, b, 0, s, a, recs, flows, opt, order, mark, tile_heads, tile_brk, tile_bytes);
     hipLaunchKernelGGL(k_tile_scan<uint32_t>, dim3(1), b, 0, s, tile_heads, tiles, out_count);

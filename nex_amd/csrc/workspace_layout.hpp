@@ -1,0 +1,84 @@
+// workspace_layout.hpp — where the regions of a caller's workspace start.
+//
+// include/nexg.h gives each workspace's size (the nexg_*_workspace inlines, a C
+// header other people compile); the structs here name the regions inside and
+// give their byte offsets, and the launchers of nexg_flow.hip take every
+// pointer from them. tests/native/workspace_layout_test.cpp holds the two
+// against each other: equal sizes, regions aligned, disjoint and in bounds.
+// Plain host code: <stdint.h> and nexg.h only.
+#pragma once
+#include <stdint.h>
+
+#include "../../include/nexg.h"
+
+namespace nexg {
+
+template <typename T>
+inline T* region(void* workspace, uint64_t offset) {
+    return reinterpret_cast<T*>(static_cast<char*>(workspace) + offset);
+}
+
+// nexg_flow_partition_workspace: the scan's total, one u32 per chunk of 1024
+// counters (an even number of slots, so the counters start on 8 B), then the
+// buckets x tiles counters, bucket-major
+struct FlowPartLayout {
+    static constexpr uint32_t kChunk = 1024u;  // counters per chunk of the scan
+    uint64_t tiles, counters, chunks;
+    uint64_t total;  // u64[1]
+    uint64_t sums;   // u32[chunks]
+    uint64_t hist;   // u32[counters]
+    uint64_t bytes;
+    static FlowPartLayout from(uint64_t count, uint32_t buckets) {
+        FlowPartLayout w;
+        w.tiles = (count + NEXG_FLOW_TILE - 1u) / NEXG_FLOW_TILE;
+        w.counters = w.tiles * buckets;
+        w.chunks = (w.counters + kChunk - 1u) / kChunk;
+        w.total = 0;
+        w.sums = 8u;
+        w.hist = w.sums + 4u * ((w.chunks + 1u) & ~(uint64_t)1u);
+        w.bytes = w.hist + 4u * w.counters;
+        return w;
+    }
+};
+
+// nexg_flow_sort_workspace: the partition's at 256 buckets (a whole number of
+// 8 B), then two buffers of `count` (hash, index) pairs
+struct FlowSortLayout : FlowPartLayout {
+    uint64_t ping, pong;  // u64[count] each
+    static FlowSortLayout from(uint64_t count) {
+        FlowSortLayout w;
+        static_cast<FlowPartLayout&>(w) = FlowPartLayout::from(count, 256u);
+        w.ping = w.bytes;
+        w.pong = w.ping + 8u * count;
+        w.bytes = w.pong + 8u * count;
+        return w;
+    }
+};
+
+// nexg_flow_groups_workspace: the 8-B regions first, the u32 tables (an even
+// number of slots each) behind them
+struct FlowGroupsLayout {
+    uint64_t tiles;       // of 256 sorted positions
+    uint64_t totals;      // u64[2]: breaks, bytes
+    uint64_t tile_bytes;  // u64[tiles]
+    uint64_t mark;        // u64[count]
+    uint64_t tile_heads;  // u32[tiles]
+    uint64_t tile_brk;    // u32[tiles]
+    uint64_t starts;      // u32[count]
+    uint64_t bytes;
+    static FlowGroupsLayout from(uint64_t count) {
+        FlowGroupsLayout w;
+        w.tiles = (count + 255u) / 256u;
+        const uint64_t even_tiles = (w.tiles + 1u) & ~(uint64_t)1u;
+        w.totals = 0;
+        w.tile_bytes = 16u;
+        w.mark = w.tile_bytes + 8u * w.tiles;
+        w.tile_heads = w.mark + 8u * count;
+        w.tile_brk = w.tile_heads + 4u * even_tiles;
+        w.starts = w.tile_brk + 4u * even_tiles;
+        w.bytes = w.starts + 4u * ((count + 1u) & ~(uint64_t)1u);
+        return w;
+    }
+};
+
+}  // namespace nexg

@@ -42,6 +42,17 @@ def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _frames(batch):
+    """The nexg_frames argument of a call (it keeps the structure alive)."""
+    return ctypes.byref(batch.to_c())
+
+
+def _ordered(batch):
+    """Whether a table derived from `batch` frame by frame is monotone: the
+    batch is fixed-stride, packed or itself carries FRAMES_MONOTONE."""
+    return batch.offsets is None or batch.lengths is None or bool(batch.hints & abi.FRAMES_MONOTONE)
+
+
 @dataclass
 class FrameBatch:
     """A device-resident batch of raw frames (nexg_frames).
@@ -189,6 +200,17 @@ class Engine:
         if rc != abi.OK:
             raise NexgError(rc, self.lib.nexg_ctx_last_error(self.ctx).decode())
 
+    def _table(self, count):
+        """The (index, off, len) tensors of a derived table: max(count, 1) rows."""
+        torch = _torch()
+        n, dev = max(count, 1), self.torch_device
+        return (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int64, device=dev),
+                torch.empty(n, dtype=torch.int32, device=dev))
+
+    def _workspace(self, nbytes):
+        """A workspace of at least `nbytes`, 8-B aligned."""
+        return _torch().empty((nbytes + 7) // 8, dtype=_torch().int64, device=self.torch_device)
+
     # --- hot path -------------------------------------------------------
     def parse(self, batch: FrameBatch, option: ParseOption = ParseOption(),
               mode: ParseMode = ParseMode.Lenient, out_kind: int = abi.OUT_DESC,
@@ -207,9 +229,8 @@ class Engine:
         elif out.numel() * out.element_size() < nbytes or out.device != self.torch_device:
             raise ValueError(f"out holds {out.numel() * out.element_size()} B on {out.device}; "
                              f"{nbytes} B on {self.torch_device} needed")
-        fr = batch.to_c()
         opt = abi.ParseOptionC(option.flags(mode), option.offset)
-        self._check(self.lib.nexg_parse_batch(self.ctx, ctypes.byref(fr), ctypes.byref(opt), out_kind,
+        self._check(self.lib.nexg_parse_batch(self.ctx, _frames(batch), ctypes.byref(opt), out_kind,
                                               _ptr(out), self._stream(stream)))
         return out
 
@@ -245,10 +266,9 @@ class Engine:
         torch = _torch()
         if out is None:
             out = torch.empty(max(batch.count, 1) * 8, dtype=torch.uint8, device=self.torch_device)
-        fr = batch.to_c()
         opt = abi.ParseOptionC(option.flags(mode), option.offset)
         fn = self.lib.nexg_grouped_expand if grouped else self.lib.nexg_sparse_expand
-        self._check(fn(self.ctx, ctypes.byref(fr), ctypes.byref(opt), _ptr(sparse), _ptr(out), self._stream(stream)))
+        self._check(fn(self.ctx, _frames(batch), ctypes.byref(opt), _ptr(sparse), _ptr(out), self._stream(stream)))
         return out
 
     def recompute_checksums(self, batch: FrameBatch, which: int = abi.FIX_IP | abi.FIX_L4,
@@ -259,9 +279,8 @@ class Engine:
         Returns the nexg_fixup[count] report (uint8 device tensor) or None."""
         torch = _torch()
         out = torch.empty(max(batch.count, 1) * 8, dtype=torch.uint8, device=self.torch_device) if report else None
-        fr = batch.to_c()
         opt = abi.ParseOptionC(option.flags(ParseMode.Lenient), option.offset)
-        self._check(self.lib.nexg_recompute_checksums_batch(self.ctx, ctypes.byref(fr), ctypes.byref(opt), which,
+        self._check(self.lib.nexg_recompute_checksums_batch(self.ctx, _frames(batch), ctypes.byref(opt), which,
                                                             _ptr(out), self._stream(stream)))
         return out
 
@@ -271,8 +290,7 @@ class Engine:
         the uint8 device tensor a NEXG_OUT_RECORD parse of `batch` returned."""
         torch = _torch()
         out = torch.empty(max(batch.count, 1) * 96, dtype=torch.uint8, device=self.torch_device)
-        fr = batch.to_c()
-        self._check(self.lib.nexg_decode_options(self.ctx, ctypes.byref(fr), _ptr(records), _ptr(out),
+        self._check(self.lib.nexg_decode_options(self.ctx, _frames(batch), _ptr(records), _ptr(out),
                                                  self._stream(stream)))
         return out
 
@@ -303,13 +321,11 @@ class Engine:
         tunnels = torch.empty(n * 16, dtype=torch.uint8, device=self.torch_device)
         off = torch.empty(n, dtype=torch.int64, device=self.torch_device)
         ln = torch.empty(n, dtype=torch.int32, device=self.torch_device)
-        fr = batch.to_c()
         opt = abi.DecapOption(which, vxlan_port, 0)
-        self._check(self.lib.nexg_decap_batch(self.ctx, ctypes.byref(fr), _ptr(records), ctypes.byref(opt),
+        self._check(self.lib.nexg_decap_batch(self.ctx, _frames(batch), _ptr(records), ctypes.byref(opt),
                                               _ptr(tunnels), _ptr(off), _ptr(ln), self._stream(stream)))
-        ordered = batch.offsets is None or batch.lengths is None or bool(batch.hints & abi.FRAMES_MONOTONE)
         inner = FrameBatch(data=batch.data, count=batch.count, offsets=off[: batch.count], lengths=ln[: batch.count],
-                           hints=abi.FRAMES_MONOTONE if ordered else 0)
+                           hints=abi.FRAMES_MONOTONE if _ordered(batch) else 0)
         return tunnels[: batch.count * 16], inner
 
     def decap_select(self, tunnels, inner: FrameBatch, classes, stream=None):
@@ -327,14 +343,10 @@ class Engine:
         for c in classes:
             mask |= 1 << int(c)
         count = inner.count
-        n = max(count, 1)
-        dev = self.torch_device
-        idx = torch.empty(n, dtype=torch.int32, device=dev)
-        off = torch.empty(n, dtype=torch.int64, device=dev)
-        ln = torch.empty(n, dtype=torch.int32, device=dev)
-        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        idx, off, ln = self._table(count)
+        cnt = torch.zeros(1, dtype=torch.int64, device=self.torch_device)
         ws_bytes = abi.decap_select_workspace(count)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        ws = self._workspace(ws_bytes)
         self._check(self.lib.nexg_decap_select(self.ctx, _ptr(tunnels), _ptr(inner.offsets), _ptr(inner.lengths), count,
                                                mask, _ptr(idx), _ptr(off), _ptr(ln), _ptr(cnt), _ptr(ws), ws_bytes,
                                                self._stream(stream)))
@@ -367,23 +379,18 @@ class Engine:
         torch = _torch()
         fc = flt.to_c()  # ValueError for what nexg_select_batch rejects
         count = batch.count
-        n = max(count, 1)
         dev = self.torch_device
-        idx = torch.empty(n, dtype=torch.int32, device=dev)
-        off = torch.empty(n, dtype=torch.int64, device=dev)
-        ln = torch.empty(n, dtype=torch.int32, device=dev)
-        rule = torch.empty(n, dtype=torch.uint8, device=dev) if want_rule else None
+        idx, off, ln = self._table(count)
+        rule = torch.empty(max(count, 1), dtype=torch.uint8, device=dev) if want_rule else None
         cnt = torch.zeros(1, dtype=torch.int64, device=dev)
         ws_bytes = abi.select_workspace(count)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        fr = batch.to_c()
-        self._check(self.lib.nexg_select_batch(self.ctx, ctypes.byref(fr), _ptr(records), ctypes.byref(fc), _ptr(idx),
+        ws = self._workspace(ws_bytes)
+        self._check(self.lib.nexg_select_batch(self.ctx, _frames(batch), _ptr(records), ctypes.byref(fc), _ptr(idx),
                                                _ptr(off), _ptr(ln), _ptr(rule), _ptr(cnt), _ptr(ws), ws_bytes,
                                                self._stream(stream)))
         k = int(cnt.item())  # waits for the kernels
-        ordered = batch.offsets is None or batch.lengths is None or bool(batch.hints & abi.FRAMES_MONOTONE)
         sel = FrameBatch(data=batch.data, count=k, offsets=off[:k], lengths=ln[:k],
-                         hints=abi.FRAMES_MONOTONE if ordered else 0)
+                         hints=abi.FRAMES_MONOTONE if _ordered(batch) else 0)
         return (idx[:k], sel, rule[:k]) if want_rule else (idx[:k], sel)
 
     def gather(self, sel: FrameBatch, align: int = 1, stream=None):
@@ -402,14 +409,13 @@ class Engine:
         offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
         ln = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if align != 1 else None
         ws_bytes = abi.gather_plan_workspace(n)
-        ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dev)
-        fr = sel.to_c()
+        ws = self._workspace(ws_bytes)
+        fr = _frames(sel)
         s = self._stream(stream)
-        self._check(self.lib.nexg_gather_plan(self.ctx, ctypes.byref(fr), align, _ptr(offs), _ptr(ln), _ptr(ws),
-                                              ws_bytes, s))
+        self._check(self.lib.nexg_gather_plan(self.ctx, fr, align, _ptr(offs), _ptr(ln), _ptr(ws), ws_bytes, s))
         total = int(offs[n].item())  # waits for the kernels
         data = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
-        self._check(self.lib.nexg_gather_frames(self.ctx, ctypes.byref(fr), _ptr(offs), _ptr(data), total, s))
+        self._check(self.lib.nexg_gather_frames(self.ctx, fr, _ptr(offs), _ptr(data), total, s))
         return FrameBatch(data=data[:total], count=n, offsets=offs, lengths=None if ln is None else ln[:n],
                           hints=0 if ln is None else abi.FRAMES_MONOTONE)
 
@@ -455,8 +461,7 @@ class Engine:
         torch = _torch()
         fo = (option if option is not None else FlowOption()).to_c()  # ValueError for what nexg_flow_batch rejects
         out = torch.empty(max(batch.count, 1) * 8, dtype=torch.uint8, device=self.torch_device)
-        fr = batch.to_c()
-        self._check(self.lib.nexg_flow_batch(self.ctx, ctypes.byref(fr), _ptr(records), ctypes.byref(fo), _ptr(out),
+        self._check(self.lib.nexg_flow_batch(self.ctx, _frames(batch), _ptr(records), ctypes.byref(fo), _ptr(out),
                                              self._stream(stream)))
         return out[: batch.count * 8]
 
@@ -478,20 +483,15 @@ class Engine:
         if not 1 <= int(buckets) <= abi.FLOW_MAX_BUCKETS:
             raise ValueError("buckets must be 1..256")
         count = batch.count
-        n = max(count, 1)
-        dev = self.torch_device
-        idx = torch.empty(n, dtype=torch.int32, device=dev)
-        off = torch.empty(n, dtype=torch.int64, device=dev)
-        ln = torch.empty(n, dtype=torch.int32, device=dev)
-        first = torch.empty(buckets + 1, dtype=torch.int64, device=dev)
+        idx, off, ln = self._table(count)
+        first = torch.empty(buckets + 1, dtype=torch.int64, device=self.torch_device)
         ws_bytes = abi.flow_partition_workspace(count, buckets)
-        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
-        fr = batch.to_c()
-        self._check(self.lib.nexg_flow_partition(self.ctx, ctypes.byref(fr), _ptr(flows), int(buckets), _ptr(idx),
+        ws = self._workspace(ws_bytes)
+        self._check(self.lib.nexg_flow_partition(self.ctx, _frames(batch), _ptr(flows), int(buckets), _ptr(idx),
                                                  _ptr(off), _ptr(ln), _ptr(first), _ptr(ws), ws_bytes,
                                                  self._stream(stream)))
         host_first = first.cpu().numpy()  # waits for the kernels
-        ordered = batch.offsets is None or batch.lengths is None or bool(batch.hints & abi.FRAMES_MONOTONE)
+        ordered = _ordered(batch)
         # monotone inside each bucket (Engine.flow_bucket's views), not across bucket boundaries
         table = FrameBatch(data=batch.data, count=count, offsets=off[:count], lengths=ln[:count],
                            hints=abi.FRAMES_MONOTONE if ordered and buckets == 1 else 0,
@@ -516,10 +516,9 @@ class Engine:
         entries. Allocates the workspace; no synchronisation."""
         torch = _torch()
         count = flows.numel() * flows.element_size() // 8
-        dev = self.torch_device
-        idx = torch.empty(max(count, 1), dtype=torch.int32, device=dev)
+        idx = torch.empty(max(count, 1), dtype=torch.int32, device=self.torch_device)
         ws_bytes = abi.flow_sort_workspace(count)
-        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
+        ws = self._workspace(ws_bytes)
         self._check(self.lib.nexg_flow_sort(self.ctx, _ptr(flows), count, _ptr(idx), _ptr(ws), ws_bytes,
                                             self._stream(stream)))
         return idx[:count]
@@ -559,12 +558,12 @@ class Engine:
         group_of = torch.empty(max(count, 1), dtype=torch.int32, device=dev)
         cnt = torch.zeros(1, dtype=torch.int64, device=dev)
         ws_bytes = abi.flow_groups_workspace(count)
-        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=dev)
-        fr = batch.to_c()
+        ws = self._workspace(ws_bytes)
+        fr = _frames(batch)
         s = self._stream(stream)
 
         def run(rows, cap, gof):
-            self._check(self.lib.nexg_flow_groups(self.ctx, ctypes.byref(fr), _ptr(records), _ptr(flows), ctypes.byref(fo),
+            self._check(self.lib.nexg_flow_groups(self.ctx, fr, _ptr(records), _ptr(flows), ctypes.byref(fo),
                                                   _ptr(order), _ptr(rows), cap, _ptr(gof), _ptr(cnt), _ptr(ws), ws_bytes, s))
 
         if groups_cap is not None:
@@ -605,18 +604,17 @@ class Engine:
         dev = self.torch_device
         out = torch.empty(max(n, 1) * 32, dtype=torch.uint8, device=dev)
         tile_first = torch.empty(abi.dns_tile_first_bytes(n) // 8, dtype=torch.int64, device=dev)
-        fr = batch.to_c()
+        fr = _frames(batch)
         opt = abi.DnsOption(abi.DNS_ANY_UDP if any_udp else 0, port, 0)
         s = self._stream(stream)
-        self._check(self.lib.nexg_dns_batch(self.ctx, ctypes.byref(fr), _ptr(records), ctypes.byref(opt), _ptr(out),
+        self._check(self.lib.nexg_dns_batch(self.ctx, fr, _ptr(records), ctypes.byref(opt), _ptr(out),
                                             _ptr(tile_first), s))
         if entries_cap is None:
             total = cap = int(tile_first[-1].item())  # waits for the kernels
         else:
             total, cap = tile_first[-1:], int(entries_cap)
         entries = torch.empty(max(cap, 1) * 16, dtype=torch.uint8, device=dev)
-        self._check(self.lib.nexg_dns_entries(self.ctx, ctypes.byref(fr), _ptr(out), _ptr(tile_first), _ptr(entries),
-                                              cap, s))
+        self._check(self.lib.nexg_dns_entries(self.ctx, fr, _ptr(out), _ptr(tile_first), _ptr(entries), cap, s))
         return out[: n * 32], tile_first, entries[: cap * 16], total
 
     def probe_stream(self, data, write8, out=None, stream=None):
@@ -654,9 +652,8 @@ class Engine:
             out = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=self.torch_device)
         nwg = max(1, (batch.count + 255) // 256)
         stamps = torch.zeros((nwg, 8), dtype=torch.int64, device=self.torch_device)
-        fr = batch.to_c()
         opt = abi.ParseOptionC(option.flags(mode), option.offset)
-        self._check(self.lib.nexg_probe_span_clock(self.ctx, ctypes.byref(fr), ctypes.byref(opt), _ptr(out),
+        self._check(self.lib.nexg_probe_span_clock(self.ctx, _frames(batch), ctypes.byref(opt), _ptr(out),
                                                    _ptr(stamps), self._stream(stream)))
         return out, stamps
 
@@ -677,9 +674,8 @@ class Engine:
         """util::checksum(buf, skipword) per buffer (util.rs:65)."""
         torch = _torch()
         out = torch.empty(max(batch.count, 1), dtype=torch.int16, device=self.torch_device)
-        fr = batch.to_c()
         skip = min(int(skipword), 0xFFFFFFFF)
-        self._check(self.lib.nexg_checksum_batch(self.ctx, ctypes.byref(fr), skip, _ptr(out),
+        self._check(self.lib.nexg_checksum_batch(self.ctx, _frames(batch), skip, _ptr(out),
                                                  self._stream(stream)))
         return out[: batch.count]
 

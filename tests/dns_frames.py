@@ -21,24 +21,6 @@ OK, SHORT, BAD = abi.FRAME_OK, abi.ERR_BUFFER_TOO_SHORT, abi.ERR_MALFORMED
 CLIENT = 0xC001  # the other port of every wrapped message
 
 
-def build_cpp_dns_test():
-    """tests/native/cpp_dns_test (the C++ API's DNS wrappers), compiled with
-    the line of tests/native/Makefile's cpp_frame_test rule when it is missing
-    or older than what it is built from. Returns its path."""
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    here = os.path.join(root, "tests", "native")
-    src, exe = os.path.join(here, "cpp_dns_test.cpp"), os.path.join(here, "cpp_dns_test")
-    deps = [src, os.path.join(root, "include", "nexg.hpp"), os.path.join(root, "include", "nexg.h"),
-            os.path.join(root, "nex_amd", "libnexg.so")]
-    if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in deps):
-        return exe
-    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O1", "-std=c++17", "-Wall", "-Werror",
-                           "--offload-arch=gfx950", "-I", os.path.join(root, "include"), "-o", exe, src,
-                           "-L" + os.path.join(root, "nex_amd"), "-lnexg", "-Wl,-rpath,$ORIGIN/../../nex_amd"])
-    return exe
-
-
 def vectors():
     with open(VECTORS) as f:
         return json.load(f)

@@ -21,23 +21,6 @@ PARSE_FLAGS = sf.PARSE_FLAGS
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def build_cpp_flow_test():
-    """tests/native/cpp_flow_test (the C++ API's flow wrappers), compiled with
-    the line of tests/native/Makefile's cpp_frame_test rule when it is missing
-    or older than what it is built from. Returns its path."""
-    import subprocess
-    here = os.path.join(ROOT, "tests", "native")
-    src, exe = os.path.join(here, "cpp_flow_test.cpp"), os.path.join(here, "cpp_flow_test")
-    deps = [src, os.path.join(ROOT, "include", "nexg.hpp"), os.path.join(ROOT, "include", "nexg.h"),
-            os.path.join(ROOT, "nex_amd", "libnexg.so")]
-    if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in deps):
-        return exe
-    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O1", "-std=c++17", "-Wall", "-Werror",
-                           "--offload-arch=gfx950", "-I", os.path.join(ROOT, "include"), "-o", exe, src,
-                           "-L" + os.path.join(ROOT, "nex_amd"), "-lnexg", "-Wl,-rpath,$ORIGIN/../../nex_amd"])
-    return exe
-
-
 def vectors():
     """The golden vectors: dicts with src, sport, dst, dport, hash_l4, hash_ip (ints)."""
     with open(os.path.join(ROOT, "tests", "golden", "flow_vectors.json")) as f:

@@ -1,17 +1,13 @@
 """What the per-flow counter tests share (nexg_flow_sort / nexg_flow_groups,
-include/nexg.h): the build of tests/native/cpp_flow_groups_test, the pinned
-32-bit hash collision, and an independent reference for the groups (a dict
-group-by over the hash with a set of keys per group, on the hash and address
-code of tests/second_pass_ref.py, not nex_amd.flow.flow_key)."""
-import os
-
+include/nexg.h): the pinned 32-bit hash collision, and an independent
+reference for the groups (a dict group-by over the hash with a set of keys per
+group, on the hash and address code of tests/second_pass_ref.py, not
+nex_amd.flow.flow_key)."""
 import numpy as np
 
 from nex_amd import abi
 from tests import flow_frames as ff
 from tests import second_pass_ref as ref
-
-ROOT = ff.ROOT
 
 #: with the default key both address pairs hash to COLLISION_HASH (and, the
 #: hash being linear, to one value with equal ports appended)
@@ -19,24 +15,6 @@ COLLISION_A = ("10.0.0.1", "10.0.0.2")
 COLLISION_B = ("231.24.44.220", "10.0.0.2")
 COLLISION_HASH = 0x02B7C9B1
 COLLISION_PORTS = (1111, 2222)
-
-
-def build_cpp_flow_groups_test():
-    """tests/native/cpp_flow_groups_test (the C++ API's flow_sort /
-    flow_groups wrappers), compiled with the line of
-    tests.flow_frames.build_cpp_flow_test when it is missing or older than
-    what it is built from. Returns its path."""
-    import subprocess
-    here = os.path.join(ROOT, "tests", "native")
-    src, exe = os.path.join(here, "cpp_flow_groups_test.cpp"), os.path.join(here, "cpp_flow_groups_test")
-    deps = [src, os.path.join(ROOT, "include", "nexg.hpp"), os.path.join(ROOT, "include", "nexg.h"),
-            os.path.join(ROOT, "nex_amd", "libnexg.so")]
-    if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in deps):
-        return exe
-    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O1", "-std=c++17", "-Wall", "-Werror",
-                           "--offload-arch=gfx950", "-I", os.path.join(ROOT, "include"), "-o", exe, src,
-                           "-L" + os.path.join(ROOT, "nex_amd"), "-lnexg", "-Wl,-rpath,$ORIGIN/../../nex_amd"])
-    return exe
 
 
 def collision_frames(pattern="ABAAB"):

@@ -23,6 +23,16 @@ def golden():
         return json.load(f)
 
 
+def build_native_test(name):
+    """tests/native/<name> (cpp_decap_test, workspace_layout_test, ...), made by
+    tests/native/Makefile when it is missing or older than what it is built
+    from; __graft_entry__.build() makes them too. Returns its path."""
+    import subprocess
+    here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native")
+    subprocess.check_call(["make", "-s", "-C", here, name])
+    return os.path.join(here, name)
+
+
 def rfc1071(data: bytes) -> int:
     """Independent Internet checksum (RFC 1071) of `data` (pure Python)."""
     if len(data) % 2:
@@ -159,6 +169,65 @@ def records_equal(a: np.ndarray, b: np.ndarray, frames=None, what=""):
         fr = "" if frames is None else bytes(frames[i]).hex()
         raise AssertionError(f"{what}: {len(bad)} of {len(a)} records differ; first #{i}: "
                              f"{detail} frame={fr}")
+
+
+# ---- device batches of the second-pass GPU tests ----------------------------------
+
+def packed_from_byte_1(frames):
+    """Packed layout whose first frame starts one byte into the allocation:
+    headers at every byte alignment. (The data pointer itself stays 4-B
+    aligned, as nexg_frames requires: the shift is in the offsets.)"""
+    import torch
+    from nex_amd.engine import FrameBatch
+    offs = np.zeros(len(frames) + 1, np.int64)
+    offs[1:] = np.cumsum([len(f) for f in frames])
+    offs += 1
+    buf = np.zeros(int(offs[-1]) + 16, np.uint8)
+    buf[1:int(offs[-1])] = np.frombuffer(b"".join(frames), np.uint8)
+    dev = torch.from_numpy(buf).cuda()
+    return FrameBatch(data=dev[: int(offs[-1])], count=len(frames), offsets=torch.from_numpy(offs).cuda())
+
+
+def strided(frames):
+    from nex_amd.engine import FrameBatch
+    stride = (max([len(f) for f in frames] + [16]) + 15) // 16 * 16
+    a = np.zeros((len(frames), stride), np.uint8)
+    for i, f in enumerate(frames):
+        a[i, :len(f)] = np.frombuffer(f, np.uint8)
+    return FrameBatch.from_strided(a, lengths=[len(f) for f in frames])
+
+
+def layouts(frames, only_first=False, strided_below=4096):
+    """(name, batch, keep) per layout: keep = the indices of `frames` the
+    batch holds (None: all). The fixed-stride batch leaves frames of
+    `strided_below` bytes or more out (a corpus with a 65535-byte frame);
+    strided_below=None keeps them all."""
+    from nex_amd.engine import FrameBatch
+    out = [("packed pad 1 from byte 1", packed_from_byte_1(frames), None)]
+    if only_first:
+        return out
+    out += [("packed pad 1 shift 4", FrameBatch.from_packed(frames, pad_to=1, shift=4), None),
+            ("offsets + lengths pad 4", FrameBatch.from_frames(frames, pad_to=4), None)]
+    if frames:
+        if strided_below is None:
+            out.append(("strided", strided(frames), None))
+        else:
+            keep = np.array([i for i, f in enumerate(frames) if len(f) < strided_below])
+            out.append(("strided", strided([frames[i] for i in keep]), keep))
+        out.append(("packed offsets32", out[0][1].with_offsets32(), None))
+        out.append(("offsets32 + lengths", out[2][1].with_offsets32(), None))
+    return out
+
+
+def to_host(t, dtype, count):
+    return t.cpu().numpy().view(np.uint8)[: count * np.dtype(dtype).itemsize].view(dtype).copy()
+
+
+def parse_records(engine, batch):
+    """The device records the select and flow corpora are parsed into (VLAN
+    unwrapped, strict: select_frames.PARSE_FLAGS)."""
+    from nex_amd.frame import ParseMode, ParseOption
+    return engine.parse(batch, ParseOption(unwrap_vlan=True), ParseMode.Strict, out_kind=abi.OUT_RECORD)
 
 
 # ---- malformed / edge-case mixes (SURVEY.md App. C "malformed mix") ---------

@@ -8,7 +8,6 @@ NEXG_PARSE_STRICT: strict mode is what makes each ParseError kind appear.
 RULES is the table of rules the GPU tests run; tests/test_select_host.py
 asserts that each selects some but not all of the corpus."""
 import ipaddress
-import os
 from dataclasses import dataclass, field
 from typing import Optional
 
@@ -26,24 +25,6 @@ A4, B4, C4, D4, E4 = "10.0.0.1", "10.1.2.3", "192.168.1.10", "172.16.0.5", "11.0
 A6, B6, C6 = "2001:db8::1", "2001:db8:1::2", "fe80::1"
 X6 = "2001:db8:aaaa:bbbb:cccc:dddd:eeee:ffff"  # the address the prefix-bit frames vary
 PREFIX_BITS = (1, 31, 32, 33, 64, 127, 128)
-
-
-def build_cpp_select_test():
-    """tests/native/cpp_select_test (the C++ API's select / gather wrappers),
-    compiled with the line of tests/native/Makefile's cpp_frame_test rule when
-    it is missing or older than what it is built from. Returns its path."""
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    here = os.path.join(root, "tests", "native")
-    src, exe = os.path.join(here, "cpp_select_test.cpp"), os.path.join(here, "cpp_select_test")
-    deps = [src, os.path.join(root, "include", "nexg.hpp"), os.path.join(root, "include", "nexg.h"),
-            os.path.join(root, "nex_amd", "libnexg.so")]
-    if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in deps):
-        return exe
-    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O1", "-std=c++17", "-Wall", "-Werror",
-                           "--offload-arch=gfx950", "-I", os.path.join(root, "include"), "-o", exe, src,
-                           "-L" + os.path.join(root, "nex_amd"), "-lnexg", "-Wl,-rpath,$ORIGIN/../../nex_amd"])
-    return exe
 
 
 def ip(a) -> bytes:

@@ -10,11 +10,11 @@ import pytest
 
 from nex_amd import abi
 
-from tests.tunnel_frames import build_cpp_decap_test as build_exe  # built by __graft_entry__.build() too
+from tests.helpers import build_native_test  # __graft_entry__.build() makes it too
 
 
 def test_cpp_decap_compiles_and_links():
-    exe = build_exe()
+    exe = build_native_test("cpp_decap_test")
     r = subprocess.run([exe, "--link"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.split() == ["link", "ok", "3", str(abi.decap_select_workspace(65793)),
@@ -27,7 +27,7 @@ def test_cpp_decap_gpu(engine, tmp_path):
     from nex_amd.engine import FrameBatch
     from nex_amd.frame import ParseOption
     from tests import tunnel_frames as tf
-    exe = build_exe()
+    exe = build_native_test("cpp_decap_test")
     cs = tf.cycled(tf.cases(), 65)
     frames = [c.frame for c in cs]
     p = tmp_path / "frames.txt"

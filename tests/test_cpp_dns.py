@@ -10,11 +10,11 @@ import pytest
 
 from nex_amd import abi
 
-from tests.dns_frames import build_cpp_dns_test as build_exe  # built by __graft_entry__.build() too
+from tests.helpers import build_native_test  # __graft_entry__.build() makes it too
 
 
 def test_cpp_dns_compiles_and_links():
-    exe = build_exe()
+    exe = build_native_test("cpp_dns_test")
     r = subprocess.run([exe, "--link"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.split() == ["link", "ok", "3", "10", str(abi.dns_tile_first_bytes(65537)),
@@ -24,7 +24,7 @@ def test_cpp_dns_compiles_and_links():
 @pytest.mark.gpu
 def test_cpp_dns_gpu(tmp_path):
     from tests import dns_frames as df
-    exe = build_exe()
+    exe = build_native_test("cpp_dns_test")
     cs = df.cycled(df.cases(), 65)
     frames = [c.frame for c in cs]
     p = tmp_path / "frames.txt"

@@ -12,11 +12,11 @@ import pytest
 from nex_amd import abi
 from nex_amd.flow import FlowOption, flows_host, partition_host
 
-from tests.flow_frames import build_cpp_flow_test as build_exe  # built by __graft_entry__.build() too
+from tests.helpers import build_native_test  # __graft_entry__.build() makes it too
 
 
 def test_cpp_flow_compiles_and_links():
-    exe = build_exe()
+    exe = build_native_test("cpp_flow_test")
     r = subprocess.run([exe, "--link"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.split() == ["link", "ok", "3", str(abi.FLOW_SYMMETRIC | abi.FLOW_KEY), "7",
@@ -27,7 +27,7 @@ def test_cpp_flow_compiles_and_links():
 @pytest.mark.gpu
 def test_cpp_flow_gpu(oracle, tmp_path):
     from tests import flow_frames as ff
-    exe = build_exe()
+    exe = build_native_test("cpp_flow_test")
     frames = [x.frame for x in ff.small_corpus()]
     recs = oracle.parse_frames(frames, ff.PARSE_FLAGS)
     p = tmp_path / "frames.txt"

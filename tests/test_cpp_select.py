@@ -14,11 +14,11 @@ from nex_amd import abi
 from nex_amd import select as S
 from nex_amd.select import Filter, Rule
 
-from tests.select_frames import build_cpp_select_test as build_exe  # built by __graft_entry__.build() too
+from tests.helpers import build_native_test  # __graft_entry__.build() makes it too
 
 
 def test_cpp_select_compiles_and_links():
-    exe = build_exe()
+    exe = build_native_test("cpp_select_test")
     r = subprocess.run([exe, "--link"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.split() == ["link", "ok", "5", "5", "3", "3", str(abi.select_workspace(65793)),
@@ -28,7 +28,7 @@ def test_cpp_select_compiles_and_links():
 @pytest.mark.gpu
 def test_cpp_select_gpu(oracle, tmp_path):
     from tests import select_frames as sf
-    exe = build_exe()
+    exe = build_native_test("cpp_select_test")
     frames = [x.frame for x in sf.small_corpus()]
     recs = oracle.parse_frames(frames, sf.PARSE_FLAGS)
     p = tmp_path / "frames.txt"

@@ -26,6 +26,7 @@ from nex_amd import flow as hostflow
 from nex_amd.flow import FlowOption, groups_host, sort_host
 from tests import flow_frames as ff
 from tests import flow_group_frames as fg
+from tests import helpers
 from tests import second_pass_fuzz as fz
 from tests import second_pass_ref as ref
 from tests.test_second_pass_mutants import variant
@@ -142,7 +143,7 @@ def test_a_callers_order(hand):
 
 
 def test_abi_matches_the_header():
-    exe = fg.build_cpp_flow_groups_test()
+    exe = helpers.build_native_test("cpp_flow_groups_test")
     r = subprocess.run([exe, "--link"] + [str(c) for c in WORKSPACE_COUNTS], capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = r.stdout.splitlines()

@@ -18,6 +18,7 @@ from nex_amd.engine import FrameBatch
 from nex_amd.frame import ParseOption
 from tests import helpers
 from tests import tunnel_frames as tf
+from tests.helpers import layouts, to_host
 
 pytestmark = pytest.mark.gpu
 
@@ -43,47 +44,10 @@ def corpus(oracle):
     return cases, want, ids
 
 
-def packed_from_byte_1(frames):
-    """Packed layout whose first frame starts one byte into the allocation:
-    tunnel headers at every byte alignment. (The data pointer itself stays
-    4-B aligned, as nexg_frames requires: the shift is in the offsets.)"""
-    import torch
-    offs = np.zeros(len(frames) + 1, np.int64)
-    offs[1:] = np.cumsum([len(f) for f in frames])
-    offs += 1
-    buf = np.zeros(int(offs[-1]) + 16, np.uint8)
-    buf[1:int(offs[-1])] = np.frombuffer(b"".join(frames), np.uint8)
-    dev = torch.from_numpy(buf).cuda()
-    return FrameBatch(data=dev[: int(offs[-1])], count=len(frames), offsets=torch.from_numpy(offs).cuda())
-
-
-def strided(frames):
-    stride = (max([len(f) for f in frames] + [16]) + 15) // 16 * 16
-    a = np.zeros((len(frames), stride), np.uint8)
-    for i, f in enumerate(frames):
-        a[i, :len(f)] = np.frombuffer(f, np.uint8)
-    return FrameBatch.from_strided(a, lengths=[len(f) for f in frames])
-
-
-def layouts(frames):
-    out = [("packed pad 1 from byte 1", packed_from_byte_1(frames)),
-           ("packed pad 1 shift 4", FrameBatch.from_packed(frames, pad_to=1, shift=4)),
-           ("offsets + lengths pad 4", FrameBatch.from_frames(frames, pad_to=4))]
-    if frames:
-        out.append(("strided", strided(frames)))
-        out.append(("packed offsets32", out[0][1].with_offsets32()))
-        out.append(("offsets32 + lengths", out[2][1].with_offsets32()))
-    return out
-
-
 def outer_offsets(batch):
     if batch.offsets is None:
         return np.arange(batch.count, dtype=np.int64) * batch.stride
     return batch.host_offsets()[: batch.count]
-
-
-def to_host(t, dtype, count):
-    return t.cpu().numpy().view(np.uint8)[: count * np.dtype(dtype).itemsize].view(dtype).copy()
 
 
 def run_decap(engine, batch, option=VLAN, **kw):
@@ -133,7 +97,7 @@ def test_decap_every_layout(engine, corpus, count):
     cases = corpus[0]
     cs = tf.cycled(cases, count)
     frames = [c.frame for c in cs]
-    for name, batch in layouts(frames):
+    for name, batch, _ in layouts(frames, strided_below=None):
         name = f"{name} n={count}"
         recs, tunnels, inner, hrecs, htun, ioff, ilen = run_decap(engine, batch)
         check_against_host(name, frames, batch, hrecs, htun, ioff, ilen)

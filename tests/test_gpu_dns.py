@@ -19,7 +19,7 @@ from nex_amd.engine import FrameBatch
 from nex_amd.frame import ParseOption
 from tests import dns_frames as df
 from tests import helpers
-from tests.test_gpu_decap import layouts, to_host
+from tests.helpers import layouts, to_host
 
 pytestmark = pytest.mark.gpu
 
@@ -88,7 +88,7 @@ def check(name, cs, frames, hrecs, hdns, htf, hent, total, port=53, any_udp=Fals
 def test_dns_every_layout(engine, corpus, count):
     cs = df.cycled(corpus, count)
     frames = [c.frame for c in cs]
-    for name, batch in layouts(frames):
+    for name, batch, _ in layouts(frames, strided_below=None):
         _, _, _, _, total, hrecs, hdns, htf, hent = run_dns(engine, batch)
         check(f"{name} n={count}", cs, frames, hrecs, hdns, htf, hent, total)
     if count >= 63:

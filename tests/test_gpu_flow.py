@@ -22,7 +22,8 @@ from nex_amd.flow import FlowOption, flows_host, partition_host
 from nex_amd.frame import ParseMode, ParseOption
 from tests import flow_frames as ff
 from tests import helpers
-from tests.test_gpu_select import layouts, table_of, to_host
+from tests.helpers import layouts, parse_records, to_host
+from tests.test_gpu_select import table_of
 
 pytestmark = pytest.mark.gpu
 
@@ -60,10 +61,6 @@ class Corpus:
 @pytest.fixture(scope="module")
 def corp(oracle):
     return Corpus(oracle)
-
-
-def parse_records(engine, batch):
-    return engine.parse(batch, VLAN, ParseMode.Strict, out_kind=abi.OUT_RECORD)
 
 
 def flows_equal(got, want, name):

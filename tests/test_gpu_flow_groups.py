@@ -9,7 +9,7 @@ tile borders) the expectation is numpy on the test's own construction. Shapes:
 the counts around a wave, a 256-position tile, the sort's 1024-frame tile and
 its counter scan (65793 frames = 65 sort tiles and 258 group tiles; 1048577
 frames = 257 chunks of 1024 counters per digit pass, so both levels of the
-scan carry); every layout of tests/test_gpu_select.py; caller memory that
+scan carry); every layout of tests.helpers.layouts; caller memory that
 holds anything."""
 import ctypes
 import subprocess
@@ -22,8 +22,8 @@ from nex_amd.engine import FrameBatch
 from nex_amd.flow import FlowOption, flows_host, groups_host, sort_host
 from tests import flow_frames as ff
 from tests import flow_group_frames as fg
-from tests.test_gpu_flow import flows_from_hashes, parse_records
-from tests.test_gpu_select import layouts, to_host
+from tests.helpers import build_native_test, layouts, parse_records, to_host
+from tests.test_gpu_flow import flows_from_hashes
 
 pytestmark = pytest.mark.gpu
 
@@ -559,7 +559,7 @@ def test_first_records_and_buckets(engine, corp):
 
 
 def test_cpp_flow_groups_gpu(oracle, tmp_path):
-    exe = fg.build_cpp_flow_groups_test()
+    exe = build_native_test("cpp_flow_groups_test")
     frames = [x.frame for x in ff.small_corpus()] + fg.collision_frames()
     recs = oracle.parse_frames(frames, ff.PARSE_FLAGS)
     lengths = [len(f) for f in frames]

@@ -27,7 +27,8 @@ from tests import helpers
 from tests import second_pass_fuzz as fz
 from tests import second_pass_ref as ref
 from tests import tunnel_frames as tf
-from tests.test_gpu_decap import outer_offsets, packed_from_byte_1, to_host
+from tests.helpers import packed_from_byte_1, to_host
+from tests.test_gpu_decap import outer_offsets
 from tests.test_gpu_flow import dummy_batch, flows_from_hashes
 from tests.test_gpu_select import check_select
 
@@ -43,7 +44,7 @@ def corp(oracle):
 
 
 def two_layouts(frames):
-    """The first and the last layout of tests/test_gpu_decap.layouts()."""
+    """The first and the last layout of tests.helpers.layouts()."""
     return [("packed pad 1 from byte 1", packed_from_byte_1(frames)),
             ("offsets32 + lengths", FrameBatch.from_frames(frames, pad_to=4).with_offsets32())]
 

@@ -21,6 +21,7 @@ from nex_amd.frame import ParseMode, ParseOption
 from nex_amd.select import Filter, Rule
 from tests import helpers
 from tests import select_frames as sf
+from tests.helpers import layouts, parse_records, to_host
 
 pytestmark = pytest.mark.gpu
 
@@ -57,43 +58,6 @@ def corp(oracle):
     return Corpus(oracle)
 
 
-def packed_from_byte_1(frames):
-    """Packed layout whose first frame starts one byte into the allocation (the
-    data pointer stays 4-B aligned: the shift is in the offsets)."""
-    import torch
-    offs = np.zeros(len(frames) + 1, np.int64)
-    offs[1:] = np.cumsum([len(f) for f in frames])
-    offs += 1
-    buf = np.zeros(int(offs[-1]) + 16, np.uint8)
-    buf[1:int(offs[-1])] = np.frombuffer(b"".join(frames), np.uint8)
-    dev = torch.from_numpy(buf).cuda()
-    return FrameBatch(data=dev[: int(offs[-1])], count=len(frames), offsets=torch.from_numpy(offs).cuda())
-
-
-def strided(frames):
-    stride = (max([len(f) for f in frames] + [16]) + 15) // 16 * 16
-    a = np.zeros((len(frames), stride), np.uint8)
-    for i, f in enumerate(frames):
-        a[i, :len(f)] = np.frombuffer(f, np.uint8)
-    return FrameBatch.from_strided(a, lengths=[len(f) for f in frames])
-
-
-def layouts(frames, only_first=False):
-    """(name, batch, keep): keep = the indices of `frames` the batch holds
-    (None: all; the fixed-stride batch leaves the 65535-byte frame out)."""
-    out = [("packed pad 1 from byte 1", packed_from_byte_1(frames), None)]
-    if only_first:
-        return out
-    out += [("packed pad 1 shift 4", FrameBatch.from_packed(frames, pad_to=1, shift=4), None),
-            ("offsets + lengths pad 4", FrameBatch.from_frames(frames, pad_to=4), None)]
-    if frames:
-        keep = np.array([i for i, f in enumerate(frames) if len(f) < 4096])
-        out.append(("strided", strided([frames[i] for i in keep]), keep))
-        out.append(("packed offsets32", out[0][1].with_offsets32(), None))
-        out.append(("offsets32 + lengths", out[2][1].with_offsets32(), None))
-    return out
-
-
 def table_of(batch):
     """Host (offsets, lengths) of a batch as its table defines them."""
     if batch.offsets is None:
@@ -101,14 +65,6 @@ def table_of(batch):
     else:
         off = batch.host_offsets()[: batch.count]
     return off, batch.frame_lengths()
-
-
-def to_host(t, dtype, count):
-    return t.cpu().numpy().view(np.uint8)[: count * np.dtype(dtype).itemsize].view(dtype).copy()
-
-
-def parse_records(engine, batch):
-    return engine.parse(batch, VLAN, ParseMode.Strict, out_kind=abi.OUT_RECORD)
 
 
 def check_select(engine, name, batch, recs, flt, want_sel, want_rule):

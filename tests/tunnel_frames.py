@@ -17,24 +17,6 @@ from tests.helpers import _eth, _ipv4, _ipv6, _tcp
 VECTORS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "tunnel_vectors.json")
 
 
-def build_cpp_decap_test():
-    """tests/native/cpp_decap_test (the C++ API's decap wrappers), compiled with
-    the line of tests/native/Makefile's cpp_frame_test rule when it is missing
-    or older than what it is built from. Returns its path."""
-    import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    here = os.path.join(root, "tests", "native")
-    src, exe = os.path.join(here, "cpp_decap_test.cpp"), os.path.join(here, "cpp_decap_test")
-    deps = [src, os.path.join(root, "include", "nexg.hpp"), os.path.join(root, "include", "nexg.h"),
-            os.path.join(root, "nex_amd", "libnexg.so")]
-    if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in deps):
-        return exe
-    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-O1", "-std=c++17", "-Wall", "-Werror",
-                           "--offload-arch=gfx950", "-I", os.path.join(root, "include"), "-o", exe, src,
-                           "-L" + os.path.join(root, "nex_amd"), "-lnexg", "-Wl,-rpath,$ORIGIN/../../nex_amd"])
-    return exe
-
-
 def vectors():
     with open(VECTORS) as f:
         return json.load(f)
