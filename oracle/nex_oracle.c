@@ -1308,6 +1308,49 @@ int nexo_build_ndp_ns(const nexo_ip_spec* ip, uint8_t* out) {
     return wrap_ip_eth(ip, PROTO_ICMPV6, m, sizeof(m), out);
 }
 
+/* one build of nexo_build_rows with row i's fields (no builder logic of its own) */
+static int rows_one(const nexo_build_rows* p, uint64_t i, uint8_t* out) {
+    nexo_ip_spec ip = p->ip;
+    const size_t w = (p->kind == 3 || p->kind == 4 || ip.family == 4) ? 4 : 16;
+    memcpy(ip.src, p->src + w * i, w);
+    memcpy(ip.dst, p->dst + w * i, w);
+    memcpy(ip.src_mac, p->src_mac + 6 * i, 6);
+    memcpy(ip.dst_mac, p->dst_mac + 6 * i, 6);
+    if (p->ip_id) ip.ip_id = p->ip_id[i];
+    switch (p->kind) {
+    case 0:
+        return nexo_build_tcp(&ip, p->p0[i], p->p1[i], p->seq[i], p->ack[i], p->tcp_flags, p->window, p->urg,
+                              p->opts, p->opt_len, p->payload, p->payload_len, out);
+    case 1:
+        return nexo_build_icmp_echo(&ip, p->icmp_type, p->icmp_code, p->p0[i], p->p1[i], p->payload,
+                                    p->payload_len, out);
+    case 2:
+        return nexo_build_udp6(ip.src_mac, ip.dst_mac, ip.src, ip.dst, p->p0[i], p->p1[i], ip.ttl, ip.dscp_ecn,
+                               ip.flow_label, p->payload, p->payload_len, out);
+    case 3: /* addresses as the BE u32 values nexo_build_udp4 takes */
+        return nexo_build_udp4(ip.src_mac, ip.dst_mac,
+                               ((uint32_t)ip.src[0] << 24) | ((uint32_t)ip.src[1] << 16) | ((uint32_t)ip.src[2] << 8) | ip.src[3],
+                               ((uint32_t)ip.dst[0] << 24) | ((uint32_t)ip.dst[1] << 16) | ((uint32_t)ip.dst[2] << 8) | ip.dst[3],
+                               p->p0[i], p->p1[i], ip.ip_id,
+                               ip.ttl, ip.ip_flags, ip.dscp_ecn, p->payload, p->payload_len, out);
+    case 4:
+        return nexo_build_arp(ip.dst_mac, ip.src_mac, ip.src, p->target_mac + 6 * i, ip.dst, p->arp_hw_type,
+                              p->arp_proto_type, p->arp_operation, 6, 4, out);
+    default:
+        return nexo_build_ndp_ns(&ip, out);
+    }
+}
+
+int nexo_build_rows_batch(const nexo_build_rows* p, uint8_t* out) {
+    if (p->count == 0) return 0;
+    uint8_t* first = (uint8_t*)malloc(70000);
+    const int flen = rows_one(p, 0, first);
+    free(first);
+    if (flen < 0) return -1;
+    for (uint64_t i = 0; i < p->count; i++) rows_one(p, i, out + (uint64_t)flen * i);
+    return flen;
+}
+
 /* ======================= synthetic workloads =========================== */
 
 #define PHI 0x9E3779B97F4A7C15ULL

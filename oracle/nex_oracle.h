@@ -146,6 +146,31 @@ typedef struct {
 } nexo_probe_batch;
 int nexo_build_probe_batch(const nexo_probe_batch* p, uint8_t* out, int nthreads);
 
+/* One single-frame build per row, every per-frame field given per row (the
+ * builder sweep's expectation, tests/builder_sweep.py): a loop over the
+ * single-frame builders above and nothing else. kind: 0 tcp, 1 icmp echo,
+ * 2 udp over IPv6, 3 udp over IPv4, 4 arp, 5 ndp neighbour solicit. src / dst:
+ * 4 B (family 4, arp) or 16 B per row in network order; src_mac / dst_mac /
+ * target_mac 6 B per row (arp: sender, Ethernet destination, target); p0 / p1:
+ * tcp and udp source / destination port, icmp identifier / sequence. The other
+ * fields of `ip` and the L4 constants are the batch's. Frame i (flen bytes, the
+ * return value of the first build) at out + flen i. Returns flen, or -1. */
+typedef struct {
+    int kind;
+    nexo_ip_spec ip;
+    uint64_t count;
+    const uint8_t* src; const uint8_t* dst;
+    const uint8_t* src_mac; const uint8_t* dst_mac; const uint8_t* target_mac;
+    const uint16_t* ip_id; const uint16_t* p0; const uint16_t* p1;
+    const uint32_t* seq; const uint32_t* ack;
+    uint16_t window, urg;
+    uint8_t tcp_flags, icmp_type, icmp_code, pad0;
+    uint16_t arp_hw_type, arp_proto_type, arp_operation, pad1;
+    const uint8_t* opts; uint32_t opt_len;
+    const uint8_t* payload; uint32_t payload_len;
+} nexo_build_rows;
+int nexo_build_rows_batch(const nexo_build_rows* p, uint8_t* out);
+
 /* nexg_recompute_checksums_batch's semantics for one frame, in place: the
  * mutable views' recompute_checksum chained as mutable_chaining.rs:19-63. */
 void nexo_recompute_frame(uint8_t* frame, size_t len, uint32_t flags, uint32_t ip_offset, uint32_t which,

@@ -70,6 +70,8 @@ def lib():
                                       U32, P]
         L.nexo_build_probe_batch.restype = I
         L.nexo_build_probe_batch.argtypes = [ctypes.POINTER(ProbeBatch), P, I]
+        L.nexo_build_rows_batch.restype = I
+        L.nexo_build_rows_batch.argtypes = [ctypes.POINTER(BuildRows), P]
         L.nexo_recompute_frame.restype = None
         L.nexo_recompute_frame.argtypes = [P, S, U32, U32, U32, P]
         L.nexo_gen_length.restype = U32
@@ -294,6 +296,55 @@ def build_probe_batch(kind, spec, dst, nthreads=1, out=None, **l4):
         out = np.empty((n, max(flen, 1)), np.uint8)
     if n:
         lib().nexo_build_probe_batch(ctypes.byref(p), out.ctypes.data, nthreads)
+    return out
+
+
+class BuildRows(ctypes.Structure):
+    """struct nexo_build_rows (oracle/nex_oracle.h)"""
+    _fields_ = [("kind", ctypes.c_int), ("ip", IpSpec), ("count", ctypes.c_uint64),
+                ("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("src_mac", ctypes.c_void_p),
+                ("dst_mac", ctypes.c_void_p), ("target_mac", ctypes.c_void_p), ("ip_id", ctypes.c_void_p),
+                ("p0", ctypes.c_void_p), ("p1", ctypes.c_void_p), ("seq", ctypes.c_void_p), ("ack", ctypes.c_void_p),
+                ("window", ctypes.c_uint16), ("urg", ctypes.c_uint16), ("tcp_flags", ctypes.c_uint8),
+                ("icmp_type", ctypes.c_uint8), ("icmp_code", ctypes.c_uint8), ("pad0", ctypes.c_uint8),
+                ("arp_hw_type", ctypes.c_uint16), ("arp_proto_type", ctypes.c_uint16),
+                ("arp_operation", ctypes.c_uint16), ("pad1", ctypes.c_uint16),
+                ("opts", ctypes.c_void_p), ("opt_len", ctypes.c_uint32),
+                ("payload", ctypes.c_void_p), ("payload_len", ctypes.c_uint32)]
+
+
+ROWS_KIND = {"tcp": 0, "icmp": 1, "udp6": 2, "udp4": 3, "arp": 4, "ndp_ns": 5}
+
+
+def build_rows_batch(kind, spec, rows, options=b"", payload=b"", **const):
+    """One single-frame oracle build per row (nexo_build_rows_batch). `rows`
+    maps src, dst ((count, 4|16) uint8), src_mac, dst_mac ((count, 6) uint8),
+    and where the kind has them ip_id, p0, p1 (uint16: ports, or identifier /
+    sequence), seq, ack (uint32), target_mac (arp) to per-frame arrays; `spec`
+    (ip_spec) and `const` (window, urg, tcp_flags, icmp_type, icmp_code,
+    arp_hw_type, arp_proto_type, arp_operation) hold the batch's values.
+    Returns a (count, flen) uint8 array."""
+    keep = {}
+    for name, dt in (("src", np.uint8), ("dst", np.uint8), ("src_mac", np.uint8), ("dst_mac", np.uint8),
+                     ("target_mac", np.uint8), ("ip_id", np.uint16), ("p0", np.uint16), ("p1", np.uint16),
+                     ("seq", np.uint32), ("ack", np.uint32)):
+        if rows.get(name) is not None:
+            keep[name] = np.ascontiguousarray(rows[name], dt)
+    n = keep["dst"].shape[0]
+    ob, on = _buf(options)
+    pb, pn = _buf(payload)
+    p = BuildRows(kind=ROWS_KIND[kind], ip=spec, count=min(n, 1), opts=ctypes.cast(ob, ctypes.c_void_p), opt_len=on,
+                  payload=ctypes.cast(pb, ctypes.c_void_p), payload_len=pn, **const)
+    for name, a in keep.items():
+        setattr(p, name, a.ctypes.data)
+    first = ctypes.create_string_buffer(70000)
+    flen = lib().nexo_build_rows_batch(ctypes.byref(p), first) if n else 0
+    if flen < 0:
+        raise ValueError("BuildError")
+    out = np.empty((n, max(flen, 1)), np.uint8)
+    p.count = n
+    if n:
+        lib().nexo_build_rows_batch(ctypes.byref(p), out.ctypes.data)
     return out
 
 

@@ -33,6 +33,31 @@ def build_native_test(name):
     return os.path.join(here, name)
 
 
+def repeat_rows(value: bytes, n: int) -> np.ndarray:
+    """(n, len(value)) uint8: one batch-wide value as the per-frame rows
+    oracle.build_rows_batch takes."""
+    return np.tile(np.frombuffer(bytes(value), np.uint8), (n, 1))
+
+
+def udp4_expected(oracle, smac, dmac, src, dst, sport, dport, ip_id, ttl=64, ip_flags=0, dscp_ecn=0, payload=b""):
+    """(len(dst), 42 + len(payload)) uint8: the oracle's udp_ping IPv4 frame of
+    every tuple. src / sport / dport / ip_id: arrays of u32 / u16 values (signed
+    bit patterns too) or one value for the batch."""
+    n = len(dst)
+
+    def col(v, dt):
+        mask = 0xFFFFFFFF if dt == np.uint32 else 0xFFFF
+        return np.broadcast_to(np.asarray(v).astype(np.int64) & mask, (n,)).astype(dt)
+
+    def be(v):
+        return np.ascontiguousarray(col(v, np.uint32).astype(">u4")).view(np.uint8).reshape(n, 4)
+
+    rows = dict(src=be(src), dst=be(dst), src_mac=repeat_rows(smac, n), dst_mac=repeat_rows(dmac, n),
+                ip_id=col(ip_id, np.uint16), p0=col(sport, np.uint16), p1=col(dport, np.uint16))
+    spec = oracle.ip_spec(4, b"", b"", ttl=ttl, ip_flags=ip_flags, dscp_ecn=dscp_ecn)
+    return oracle.build_rows_batch("udp4", spec, rows, payload=payload)
+
+
 def rfc1071(data: bytes) -> int:
     """Independent Internet checksum (RFC 1071) of `data` (pure Python)."""
     if len(data) % 2:

@@ -33,19 +33,23 @@ def test_arp_build_matches_oracle(engine, oracle, arp_inputs, stride):
     n = len(tip)
     out = engine.build_arp(_t(tip), sender_ip=_t(sip), sender_mac=_t(smac), out_stride=stride).cpu().numpy()
     out = out[: n * stride].reshape(n, stride)
-    for i in range(0, n, 7):
-        want = oracle.build_arp(b"\xff" * 6, bytes(smac[i]), bytes(sip[i]), bytes(6), bytes(tip[i]))
-        assert out[i, :42].tobytes() == want, i
+    spec = oracle.ip_spec(4, b"", b"")
+    rows = dict(src=sip, dst=tip, src_mac=smac, dst_mac=helpers.repeat_rows(b"\xff" * 6, n),
+                target_mac=helpers.repeat_rows(bytes(6), n))
+    want = oracle.build_rows_batch("arp", spec, rows, arp_hw_type=1, arp_proto_type=0x0800, arp_operation=1)
+    bad = np.nonzero((out[:, :42] != want).any(axis=1))[0]  # every frame
+    assert bad.size == 0, bad[:8]
     if stride <= 128:  # staged tiles zero the gap after each frame; wider strides leave it as is
         assert not out[:, 42:].any()
     # per-frame target MACs and Ethernet destinations, other header words
     out = engine.build_arp(_t(tip), def_sender_ip=bytes([10, 0, 0, 1]), def_sender_mac=bytes(range(6)),
                            target_mac=_t(tmac), eth_dst=_t(smac[::-1].copy()), operation=2).cpu().numpy()
     out = out[: n * 42].reshape(n, 42)
-    for i in range(0, n, 13):
-        want = oracle.build_arp(bytes(smac[::-1][i]), bytes(range(6)), bytes([10, 0, 0, 1]), bytes(tmac[i]),
-                                bytes(tip[i]), operation=2)
-        assert out[i].tobytes() == want, i
+    rows = dict(src=helpers.repeat_rows(bytes([10, 0, 0, 1]), n), dst=tip,
+                src_mac=helpers.repeat_rows(bytes(range(6)), n), dst_mac=smac[::-1], target_mac=tmac)
+    want = oracle.build_rows_batch("arp", spec, rows, arp_hw_type=1, arp_proto_type=0x0800, arp_operation=2)
+    bad = np.nonzero((out != want).any(axis=1))[0]
+    assert bad.size == 0, bad[:8]
 
 
 def test_arp_frames_parse_back(engine, arp_inputs):
@@ -91,10 +95,12 @@ def test_ndp_ns_build_matches_oracle(engine, oracle, ns_inputs, stride, multicas
     dmac = None if multicast else bytes([0x0a, 0x0b, 0x0c, 0x0d, 0x0e, 0x0f])
     out = engine.build_ndp_ns(_t(src), _t(dst), src_mac=smac, dst_mac=dmac, out_stride=stride).cpu().numpy()
     out = out[: n * stride].reshape(n, stride)
-    for i in range(0, n, 5):
-        em = bytes([0x33, 0x33]) + bytes(dst[i, 12:16]) if multicast else dmac  # ndp.rs:25-35
-        sp = oracle.ip_spec(6, bytes(src[i]), bytes(dst[i]), src_mac=smac, dst_mac=em, ttl=255)
-        assert out[i, :86].tobytes() == oracle.build_ndp_ns(sp), i
+    em = (np.concatenate([np.full((n, 2), 0x33, np.uint8), dst[:, 12:16]], axis=1) if multicast  # ndp.rs:25-35
+          else helpers.repeat_rows(dmac, n))
+    want = oracle.build_rows_batch("ndp_ns", oracle.ip_spec(6, b"", b"", ttl=255),
+                                   dict(src=src, dst=dst, src_mac=helpers.repeat_rows(smac, n), dst_mac=em))
+    bad = np.nonzero((out[:, :86] != want).any(axis=1))[0]  # every frame
+    assert bad.size == 0, bad[:8]
     if stride <= 128:
         assert not out[:, 86:].any()
 

@@ -166,11 +166,9 @@ def test_build_udp4_matches_oracle(engine, oracle, payload_len):
     L = 42 + payload_len
     data = out.cpu().numpy()[: n * L].reshape(n, L)
     host = [t.cpu().numpy() for t in p]
-    for i in range(0, n, 97):
-        want = oracle.build_udp4(smac, dmac, int(host[0][i]) & 0xFFFFFFFF, int(host[1][i]) & 0xFFFFFFFF,
-                                 int(host[2][i]) & 0xFFFF, int(host[3][i]) & 0xFFFF,
-                                 int(host[4][i]) & 0xFFFF, 64, 2, 0, payload)
-        assert bytes(data[i]) == want, i
+    want = helpers.udp4_expected(oracle, smac, dmac, *host, ttl=64, ip_flags=2, payload=payload)
+    bad = np.nonzero((data != want).any(axis=1))[0]  # every frame
+    assert bad.size == 0, bad[:8]
     # every built frame verifies through the GPU parse path
     recs = engine.parse_to_numpy(FrameBatch(data=out, count=n, stride=L), out_kind=abi.OUT_DESC)
     assert ((recs["flags"] & (abi.C_IP_OK | abi.C_L4_OK)) == (abi.C_IP_OK | abi.C_L4_OK)).all()
@@ -200,12 +198,13 @@ def test_build_udp6_matches_oracle(engine, oracle, payload_len, stride):
                             out_stride=S)
     torch.cuda.synchronize()
     data = out.cpu().numpy()[: n * S].reshape(n, S)
-    for i in range(0, n, 13):
-        want = oracle.build_udp6(smac, dmac, bytes(src[i]), bytes(dst[i]), int(sp[i]), int(dp[i]),
-                                 61, 0x3C, 0xABCDE, payload)
-        assert bytes(data[i, :L]) == want, i
-        if S > L and S <= 128:
-            assert not data[i, L:].any(), i  # staged tiles zero the gap
+    rows = dict(src=src, dst=dst, src_mac=helpers.repeat_rows(smac, n), dst_mac=helpers.repeat_rows(dmac, n), p0=sp, p1=dp)
+    want = oracle.build_rows_batch("udp6", oracle.ip_spec(6, b"", b"", ttl=61, dscp_ecn=0x3C, flow_label=0xABCDE), rows,
+                                   payload=payload)
+    bad = np.nonzero((data[:, :L] != want).any(axis=1))[0]  # every frame
+    assert bad.size == 0, bad[:8]
+    if S > L and S <= 128:
+        assert not data[:, L:].any()  # staged tiles zero the gap
     recs = engine.parse_to_numpy(FrameBatch.from_strided(np.ascontiguousarray(data[:, :L])),
                                  out_kind=abi.OUT_DESC)
     assert (recs["flags"] & abi.C_L4_OK).all()
@@ -222,11 +221,9 @@ def test_build_udp4_strides(engine, oracle, stride):
     torch.cuda.synchronize()
     data = out.cpu().numpy()[: n * stride].reshape(n, stride)
     host = [t.cpu().numpy() for t in p]
-    for i in range(0, n, 11):
-        want = oracle.build_udp4(smac, dmac, int(host[0][i]) & 0xFFFFFFFF, int(host[1][i]) & 0xFFFFFFFF,
-                                 int(host[2][i]) & 0xFFFF, int(host[3][i]) & 0xFFFF,
-                                 int(host[4][i]) & 0xFFFF, 64, 2, 0, b"")
-        assert bytes(data[i, :42]) == want, i
+    want = helpers.udp4_expected(oracle, smac, dmac, *host, ttl=64, ip_flags=2)
+    bad = np.nonzero((data[:, :42] != want).any(axis=1))[0]  # every frame
+    assert bad.size == 0, bad[:8]
 
 
 def test_udp_ping_golden_on_gpu(engine):
@@ -389,19 +386,16 @@ def test_build_udp4_default_fields(engine, oracle):
     p = engine.gen_udp4_params(n, first_index=9)
     smac, dmac = bytes([2, 0, 0, 0, 0, 1]), bytes([2, 0, 0, 0, 0, 2])
     host = [t.cpu().numpy() for t in p]
-    for kw, pick in (({"src_port": p[2]}, lambda i: (int(host[2][i]) & 0xFFFF, 33435, 7)),
-                     ({"dst_port": p[3], "ip_id": p[4]},
-                      lambda i: (53443, int(host[3][i]) & 0xFFFF, int(host[4][i]) & 0xFFFF)),
-                     ({}, lambda i: (53443, 33435, 7))):
+    for kw, pick in (({"src_port": p[2]}, (host[2], 33435, 7)),
+                     ({"dst_port": p[3], "ip_id": p[4]}, (53443, host[3], host[4])),
+                     ({}, (53443, 33435, 7))):
         out = engine.build_udp4(p[0], p[1], def_src_port=53443, def_dst_port=33435, def_ip_id=7,
                                 src_mac=smac, dst_mac=dmac, ttl=64, ip_flags=2, **kw)
         torch.cuda.synchronize()
         data = out.cpu().numpy()[: n * 42].reshape(n, 42)
-        for i in range(0, n, 31):
-            sp, dp, ident = pick(i)
-            want = oracle.build_udp4(smac, dmac, int(host[0][i]) & 0xFFFFFFFF, int(host[1][i]) & 0xFFFFFFFF,
-                                     sp, dp, ident, 64, 2, 0, b"")
-            assert bytes(data[i]) == want, (sorted(kw), i)
+        want = helpers.udp4_expected(oracle, smac, dmac, host[0], host[1], *pick, ttl=64, ip_flags=2)
+        bad = np.nonzero((data != want).any(axis=1))[0]  # every frame
+        assert bad.size == 0, (sorted(kw), bad[:8])
     # the udp_ping probe batch (src_ip NULL: one source, ports and id from the
     # defaults, a destination per frame), at the full-tile and a ragged count
     for m in (n, 257):
@@ -409,10 +403,9 @@ def test_build_udp4_default_fields(engine, oracle):
                                 src_mac=smac, dst_mac=dmac, ttl=64, ip_flags=2)
         torch.cuda.synchronize()
         data = out.cpu().numpy()[: m * 42].reshape(m, 42)
-        for i in list(range(0, m, 29)) + [m - 1]:
-            want = oracle.build_udp4(smac, dmac, 0xC0A80164, int(host[1][i]) & 0xFFFFFFFF,
-                                     53443, 33435, 0, 64, 2, 0, b"")
-            assert bytes(data[i]) == want, ("probe", m, i)
+        want = helpers.udp4_expected(oracle, smac, dmac, 0xC0A80164, host[1][:m], 53443, 33435, 0, ttl=64, ip_flags=2)
+        bad = np.nonzero((data != want).any(axis=1))[0]  # every frame
+        assert bad.size == 0, ("probe", m, bad[:8])
 
 
 @pytest.mark.parametrize("tiles", [3, 8 * 16 * 2 + 5])
@@ -560,10 +553,9 @@ def test_build_udp4_tuples_aos(engine, oracle):
         assert torch.equal(buf_a, buf_s), (plen, shift)
         host = [t.cpu().numpy().view(np.uint32 if t.element_size() == 4 else np.uint16) for t in p]
         frames = buf_a[shift: shift + n * stride].cpu().numpy().reshape(n, stride)
-        for i in list(range(0, n, 97)) + [n - 1]:
-            want = oracle.build_udp4(smac, dmac, int(host[0][i]), int(host[1][i]), int(host[2][i]),
-                                     int(host[3][i]), int(host[4][i]), 64, 2, 0, bytes(range(plen)))
-            assert bytes(frames[i]) == want, (plen, shift, i)
+        want = helpers.udp4_expected(oracle, smac, dmac, *host, ttl=64, ip_flags=2, payload=bytes(range(plen)))
+        bad = np.nonzero((frames != want).any(axis=1))[0]  # every frame
+        assert bad.size == 0, (plen, shift, bad[:8])
     bad = abi.Udp4Build()
     bad.count, bad.dst_ip = 4, p[1].data_ptr()
     out = torch.empty(4 * 42, dtype=torch.uint8, device="cuda")

@@ -121,11 +121,12 @@ def test_udp4_probe_payload_stride(engine, oracle, plen, stride):
     torch.cuda.synchronize()
     data = out.cpu().numpy()[: n * stride].reshape(n, stride)
     hd = dst.cpu().numpy().view(np.uint32)
-    for i in list(range(0, n, 13)) + [n - 1]:
-        want = oracle.build_udp4(smac, dmac, 0xC0A80164, int(hd[i]), 53443, 33435, 9, 61, 2, 0x2e, pay)
-        assert bytes(data[i, :L]) == want, (plen, stride, i)
-        if stride <= 128:  # the LDS-staged kernels zero the gap (the direct one leaves it)
-            assert not data[i, L:].any(), (plen, stride, i)
+    want = helpers.udp4_expected(oracle, smac, dmac, 0xC0A80164, hd, 53443, 33435, 9, ttl=61, ip_flags=2, dscp_ecn=0x2e,
+                                 payload=pay)
+    bad = np.nonzero((data[:, :L] != want).any(axis=1))[0]  # every frame
+    assert bad.size == 0, (plen, stride, bad[:8])
+    if stride <= 128:  # the LDS-staged kernels zero the gap (the direct one leaves it)
+        assert not data[:, L:].any(), (plen, stride)
 
 
 @pytest.mark.parametrize("family", [4, 6])
@@ -153,10 +154,11 @@ def test_l4_probe_payload_stride(engine, oracle, family, plen, stride):
                                flow_label=0x12345, out_stride=St)
         torch.cuda.synchronize()
         data = out.cpu().numpy()[: n * St].reshape(n, St)
-        for i in list(range(0, n, 11)) + [n - 1]:
-            spec = oracle.ip_spec(family, hs, bytes(hd[i]), smac, dmac, 0x55, 33, 2, 0x10, 0x12345)
-            want = oracle.build_tcp(spec, 1234, 443, 0x01020304, 0x0a0b0c0d, 0x12, 501, 7, probes.TCP_PING_OPTS, pay)
-            assert bytes(data[i, :Lt]) == want, ("tcp", family, plen, St, i)
+        spec = oracle.ip_spec(family, hs, b"", smac, dmac, 0x55, 33, 2, 0x10, 0x12345)
+        want = oracle.build_probe_batch("tcp", spec, hd, sport=1234, dport=443, seq=0x01020304, ack=0x0a0b0c0d,
+                                        flags=0x12, window=501, urg=7, options=probes.TCP_PING_OPTS, payload=pay)
+        bad = np.nonzero((data[:, :Lt] != want).any(axis=1))[0]  # every frame
+        assert bad.size == 0, ("tcp", family, plen, St, bad[:8])
     Li = 14 + (20 if family == 4 else 40) + 8 + plen
     Si = stride or Li
     if Si >= Li:
@@ -166,10 +168,10 @@ def test_l4_probe_payload_stride(engine, oracle, family, plen, stride):
         torch.cuda.synchronize()
         data = out.cpu().numpy()[: n * Si].reshape(n, Si)
         typ = 8 if family == 4 else 128
-        for i in list(range(0, n, 11)) + [n - 1]:
-            spec = oracle.ip_spec(family, hs, bytes(hd[i]), smac, dmac, 0x99, 12, 2, 0, 0x54321)
-            want = oracle.build_icmp_echo(spec, typ, 0, 0x77, 0x88, pay)
-            assert bytes(data[i, :Li]) == want, ("icmp", family, plen, Si, i)
+        spec = oracle.ip_spec(family, hs, b"", smac, dmac, 0x99, 12, 2, 0, 0x54321)
+        want = oracle.build_probe_batch("icmp", spec, hd, icmp_type=typ, icmp_code=0, ident=0x77, seqno=0x88, payload=pay)
+        bad = np.nonzero((data[:, :Li] != want).any(axis=1))[0]  # every frame
+        assert bad.size == 0, ("icmp", family, plen, Si, bad[:8])
 
 
 @pytest.mark.parametrize("shift,stride,plen", [(1, None, 0), (1, None, 2), (0, 130, 0), (0, 200, 9), (3, 129, 5)])
@@ -192,9 +194,10 @@ def test_udp6_probe_per_lane_forms(engine, oracle, shift, stride, plen):
     torch.cuda.synchronize()
     data = out.cpu().numpy().reshape(n, S)
     hs, hd = bytes(src.cpu().numpy()), dst.cpu().numpy()
-    for i in list(range(0, n, 7)) + [n - 1]:
-        want = oracle.build_udp6(probes.SRC_MAC, probes.DST_MAC, hs, bytes(hd[i]), 53443, 33435, 64, 0, 0, pay)
-        assert bytes(data[i, :L]) == want, (shift, S, plen, i)
+    spec = oracle.ip_spec(6, hs, b"", probes.SRC_MAC, probes.DST_MAC, ttl=64)
+    want = oracle.build_probe_batch("udp6", spec, hd, sport=53443, dport=33435, payload=pay)
+    bad = np.nonzero((data[:, :L] != want).any(axis=1))[0]  # every frame
+    assert bad.size == 0, (shift, S, plen, bad[:8])
 
 
 KNOBS_CHILD = r'''
