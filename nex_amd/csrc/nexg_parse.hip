@@ -448,18 +448,7 @@ __global__ __launch_bounds__(256) void k_checksum(ParseArgs a, uint32_t skipword
         out[idx] = 0;
         return;
     }
-    const uint32_t len = (uint32_t)l64;
-    GlobalFrame f{a.data + off};
-    FrameOps<GlobalFrame> o{f, (uint32_t)((reinterpret_cast<uint64_t>(f.g)) & 1u)};
-    const uint64_t sk = 2ull * skipword;
-    uint64_t t;
-    if (sk >= len) {
-        t = o.wsum(0, len);
-    } else {
-        t = o.wsum(0, (uint32_t)sk);
-        if (sk + 2 < len) t += o.wsum((uint32_t)sk + 2u, len);
-    }
-    out[idx] = (uint16_t)fold_complement(t);
+    out[idx] = checksum_buffer(a.data + off, (uint32_t)l64, skipword);
 }
 
 hipError_t launch_checksum(const ParseArgs& a, uint32_t skipword, uint16_t* out, hipStream_t s) {

@@ -3,6 +3,7 @@
 // (nexg_parse.hip) and the kernel microbenchmarks (tools/kbench.hip).
 #pragma once
 
+#include "checksum_core.hpp"
 #include "frame_core.hpp"
 #include "nexg_internal.hpp"
 
@@ -23,17 +24,6 @@ constexpr uint32_t kTile = 256;
 // k_parse_span: bytes of the previous sub-tile kept in front (and of pad
 // behind): at least the slot, so a head window that starts there is whole
 constexpr uint32_t kApron = NEXG_SPAN_SLOT > 96 ? NEXG_SPAN_SLOT : 96;
-
-// Frame read entirely from HBM (checksum utility path).
-struct GlobalFrame {
-    NEXG_NO_DEFER
-    const uint8_t* g;
-    NEXG_HD uint32_t u8(uint32_t i) const { return g[i]; }
-    NEXG_HD uint64_t le_sum(uint32_t a, uint32_t b) const {
-        const uint64_t base = reinterpret_cast<uint64_t>(g);
-        return global_le_sum(base + a, base + b);
-    }
-};
 
 __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
     const uint32_t lane = threadIdx.x & 63u;
@@ -216,7 +206,7 @@ __device__ __forceinline__ void stage_record(uint8_t* slot, const nexg_record& r
 // NEXG_FRAMES_OFFSETS32 u32 entries, completed from the 256-frame group base
 // of frame g when the batch is over 4 GiB (g = i, or for a packed frame's end
 // the frame itself: its end lies within 4 GiB of its own group's base)
-__device__ __forceinline__ uint64_t table_off(const ParseArgs& a, uint64_t i, uint64_t g) {
+NEXG_HD uint64_t table_off(const ParseArgs& a, uint64_t i, uint64_t g) {
     if (!(a.hints & NEXG_FRAMES_OFFSETS32)) return NEXG_GLOBAL(uint64_t, a.offsets)[i];
     const uint32_t o = NEXG_GLOBAL(uint32_t, a.offsets)[i];
     if (!a.off_bases) return o;
@@ -385,7 +375,7 @@ __device__ __forceinline__ uint32_t* handoff_slot(const ParseArgs& a, uint64_t i
 // Each layout's loads in one block of uniform control flow, issued together
 // (the one-expression form compiled the packed case to offsets[idx], a wait,
 // then offsets[idx + 1]: two dependent round trips at every workgroup's start)
-__device__ __forceinline__ bool frame_extent(const ParseArgs& a, uint64_t idx, uint64_t& off, uint32_t& len) {
+NEXG_HD bool frame_extent(const ParseArgs& a, uint64_t idx, uint64_t& off, uint32_t& len) {
     uint64_t l64;
     if (a.offsets && !a.lengths && (a.hints & NEXG_FRAMES_OFFSETS32)) {  // packed, u32 table
         const auto* op = NEXG_GLOBAL(uint32_t, a.offsets);

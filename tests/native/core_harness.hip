@@ -250,3 +250,57 @@ extern "C" int harness_span_groups(const uint8_t* data, uint64_t data_bytes, con
     free(lds);
     return 0;
 }
+
+// The per-frame cores of nexg_recompute_checksums_batch and
+// nexg_checksum_batch (checksum_core.hpp) on the host, frame by frame over a
+// host table read by the kernels' own frame_extent / table_off. hints:
+// NEXG_FRAMES_OFFSETS32 for a u32 offset table, off_bases its 256-frame group
+// bases (or NULL).
+static nexg::ParseArgs host_args(const uint8_t* data, uint64_t data_bytes, const void* offsets,
+                                 const uint32_t* lengths, uint32_t stride, uint64_t count, uint32_t flags,
+                                 uint32_t ip_offset, uint32_t hints, const uint64_t* off_bases) {
+    nexg::ParseArgs a{};
+    a.data = data;
+    a.data_bytes = data_bytes;
+    a.offsets = static_cast<const uint64_t*>(offsets);
+    a.lengths = lengths;
+    a.stride = stride;
+    a.count = count;
+    a.opt_flags = flags;
+    a.ip_offset = ip_offset;
+    a.hints = hints;
+    a.off_bases = off_bases;
+    return a;
+}
+
+// k_recompute: in place over `data`; out (optional) receives the report rows
+extern "C" int harness_recompute(uint8_t* data, uint64_t data_bytes, const void* offsets, const uint32_t* lengths,
+                                 uint32_t stride, uint64_t count, uint32_t flags, uint32_t ip_offset, uint32_t hints,
+                                 const uint64_t* off_bases, uint32_t which, nexg_fixup* out) {
+    const nexg::ParseArgs a = host_args(data, data_bytes, offsets, lengths, stride, count, flags, ip_offset, hints,
+                                        off_bases);
+    for (uint64_t idx = 0; idx < count; idx++) {
+        nexg_fixup fx{0, 0, 0, 0, 0};
+        uint64_t off;
+        uint32_t len;
+        if (nexg::frame_extent(a, idx, off, len)) fx = nexg::recompute_frame(data + off, len, flags, ip_offset, which);
+        if (out) out[idx] = fx;
+    }
+    return 0;
+}
+
+// k_checksum (its extent rule restated: an empty or out-of-range buffer gives 0)
+extern "C" int harness_checksum(const uint8_t* data, uint64_t data_bytes, const void* offsets,
+                                const uint32_t* lengths, uint32_t stride, uint64_t count, uint32_t hints,
+                                const uint64_t* off_bases, uint32_t skipword, uint16_t* out) {
+    const nexg::ParseArgs a = host_args(data, data_bytes, offsets, lengths, stride, count, 0, 0, hints, off_bases);
+    for (uint64_t idx = 0; idx < count; idx++) {
+        const uint64_t off = a.offsets ? nexg::table_off(a, idx, idx) : idx * (uint64_t)a.stride;
+        const uint64_t l64 = a.lengths ? (uint64_t)a.lengths[idx]
+                                       : (a.offsets ? nexg::table_off(a, idx + 1, idx) - off : (uint64_t)a.stride);
+        const bool bad = l64 == 0 || l64 > 65535u || off > a.data_bytes || l64 > a.data_bytes - off;
+        const uint16_t c = bad ? (uint16_t)0 : nexg::checksum_buffer(data + off, (uint32_t)l64, skipword);
+        if (out) out[idx] = c;
+    }
+    return 0;
+}

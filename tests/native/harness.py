@@ -30,6 +30,10 @@ def lib():
         L.harness_tile_map.argtypes = [U32, U32, P]
         L.harness_span_groups.restype = ctypes.c_int
         L.harness_span_groups.argtypes = [P, U64, P, U64, U32, U32, P]
+        L.harness_recompute.restype = ctypes.c_int
+        L.harness_recompute.argtypes = [P, U64, P, P, U32, U64, U32, U32, U32, P, U32, P]
+        L.harness_checksum.restype = ctypes.c_int
+        L.harness_checksum.argtypes = [P, U64, P, P, U32, U64, U32, P, U32, P]
         L.harness_span_declined.restype = None
         L.harness_span_declined.argtypes = [P]
         _lib = L
@@ -118,6 +122,52 @@ def span_groups(data, offsets, flags=0, ip_offset=0, declined=None):
         lib().harness_span_declined(ctypes.c_void_p(None))
     assert rc == 0, f"harness_span_groups: {rc}"
     return recs
+
+
+def _table(data, offsets, lengths, stride, offsets32, bases):
+    """ctypes arguments of a host frame table. offsets32: the offsets go in as
+    a NEXG_FRAMES_OFFSETS32 table (u32 entries mod 2^32; bases=True adds the
+    full offset of every 256th frame, as a batch over 4 GiB carries them)."""
+    count = (len(lengths) if lengths is not None else
+             (len(offsets) - 1 if offsets is not None else len(data) // stride))
+    o64 = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+    lens = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.uint32)
+    offs, base, hints = o64, None, 0
+    if offsets32:
+        assert o64 is not None
+        offs = (o64 & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+        hints = abi.FRAMES_OFFSETS32
+        if bases:
+            base = np.ascontiguousarray(o64[::256])
+    keep = (offs, lens, base)  # alive until the call returns
+    ptr = lambda a: None if a is None else a.ctypes.data
+    return count, (ptr(offs), ptr(lens), stride, count), (hints, ptr(base)), keep
+
+
+def recompute(data, offsets=None, lengths=None, stride=0, flags=0, ip_offset=0, which=abi.FIX_IP | abi.FIX_L4,
+              offsets32=False, bases=False, report=True):
+    """k_recompute's per-frame core (checksum_core.hpp recompute_frame behind
+    frame_extent) in place over `data` (a writable contiguous uint8 array);
+    returns the nexg_fixup rows, or None with report=False."""
+    assert data.dtype == np.uint8 and data.flags.c_contiguous and data.flags.writeable
+    count, table, hints, keep = _table(data, offsets, lengths, stride, offsets32, bases)
+    out = np.zeros(max(count, 1), abi.FIXUP_DTYPE) if report else None
+    rc = lib().harness_recompute(data.ctypes.data, data.nbytes, *table, flags, ip_offset, *hints, which,
+                                 None if out is None else out.ctypes.data)
+    assert rc == 0
+    return None if out is None else out[:count]
+
+
+def checksum(data, offsets=None, lengths=None, stride=0, skipword=0, offsets32=False, bases=False):
+    """k_checksum's per-buffer core (checksum_core.hpp checksum_buffer behind
+    the kernel's extent rule): uint16[count]."""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    count, table, hints, keep = _table(data, offsets, lengths, stride, offsets32, bases)
+    out = np.zeros(max(count, 1), np.uint16)
+    rc = lib().harness_checksum(data.ctypes.data, data.nbytes, *table, *hints, min(int(skipword), 0xFFFFFFFF),
+                                out.ctypes.data)
+    assert rc == 0
+    return out[:count]
 
 
 def tile_map(nb, order):

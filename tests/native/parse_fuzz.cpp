@@ -6,7 +6,12 @@
 // six parse modes, through four window/fast-path variants: any read outside
 // the frame's chunks is a sanitizer report, any record / FrameSlice that
 // differs from the oracle's is counted. The analogue of the reference's
-// panic_free_parsing.rs. Exit 0 = clean and equal.
+// panic_free_parsing.rs. The checksum fix-up's core
+// (checksum_core.hpp recompute_frame) then runs in place on a copy of the
+// block, for three `which` values in Ethernet and two raw-IP modes, against
+// nexo_recompute_frame on another copy (bytes of the whole block and the
+// report), and checksum_buffer for five skipwords against nexo_checksum: a
+// store outside the frame is a sanitizer report too. Exit 0 = clean and equal.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -22,6 +27,12 @@ extern "C" int harness_parse(const uint8_t* data, uint64_t data_bytes, const uin
 extern "C" int harness_slice(const uint8_t* data, uint64_t data_bytes, const uint64_t* offsets,
                              const uint32_t* lengths, uint32_t stride, uint64_t count, uint32_t flags,
                              uint32_t ip_offset, uint32_t window, nexg_slice* out);
+extern "C" int harness_recompute(uint8_t* data, uint64_t data_bytes, const void* offsets, const uint32_t* lengths,
+                                 uint32_t stride, uint64_t count, uint32_t flags, uint32_t ip_offset, uint32_t hints,
+                                 const uint64_t* off_bases, uint32_t which, nexg_fixup* out);
+extern "C" int harness_checksum(const uint8_t* data, uint64_t data_bytes, const void* offsets,
+                                const uint32_t* lengths, uint32_t stride, uint64_t count, uint32_t hints,
+                                const uint64_t* off_bases, uint32_t skipword, uint16_t* out);
 
 int main(int argc, char** argv) {
     if (argc < 2) return 2;
@@ -39,6 +50,7 @@ int main(int argc, char** argv) {
                                  {NEXG_PARSE_FROM_IP, 14}, {NEXG_PARSE_FROM_IP | NEXG_PARSE_STRICT, 14},
                                  {NEXG_PARSE_VLAN, 0}};
     const int variants[][2] = {{64, 0}, {128, 1}, {80, 4}, {128, 5}};
+    const uint32_t fix_modes[][2] = {{0, 0}, {NEXG_PARSE_FROM_IP, 0}, {NEXG_PARSE_FROM_IP, 14}};
     long bad = 0, runs = 0;
     for (const auto& fr : frames) {
         for (uint32_t o : {0u, 3u, 14u}) {
@@ -65,6 +77,33 @@ int main(int argc, char** argv) {
                     fprintf(stderr, "slice differs: len %u flags %u\n", l, m[0]);
                 nexg_options opts;
                 nexo_decode_options(g, l, m[0], m[1], &opts);
+            }
+            // the fix-up core in place on a copy of the block, the oracle on another
+            for (const auto& m : fix_modes) {
+                for (uint32_t which : {(uint32_t)NEXG_FIX_IP, (uint32_t)NEXG_FIX_L4, (uint32_t)(NEXG_FIX_IP | NEXG_FIX_L4)}) {
+                    const size_t n = cap ? cap : 16;
+                    uint8_t* a = static_cast<uint8_t*>(aligned_alloc(16, n));
+                    uint8_t* b = static_cast<uint8_t*>(aligned_alloc(16, n));
+                    memcpy(a, buf, n);
+                    memcpy(b, buf, n);
+                    nexg_fixup wf, gf;
+                    memset(&gf, 0xEE, sizeof(gf));
+                    nexo_recompute_frame(b + o, l, m[0], m[1], which, &wf);
+                    harness_recompute(a + o, l, &off0, &l, 0, 1, m[0], m[1], 0, nullptr, which, &gf);
+                    runs++;
+                    if ((memcmp(a, b, n) != 0 || memcmp(&wf, &gf, sizeof(wf)) != 0) && bad++ < 5)
+                        fprintf(stderr, "fix-up differs: len %u at %u flags %u ip_offset %u which %u\n", l, o, m[0], m[1],
+                                which);
+                    free(a);
+                    free(b);
+                }
+            }
+            for (uint32_t sk : {0u, 1u, 5u, l / 2u, UINT32_MAX}) {
+                uint16_t got = 0xEEEE;
+                harness_checksum(g, l, &off0, &l, 0, 1, 0, nullptr, sk, &got);
+                runs++;
+                if (got != nexo_checksum(g, l, sk) && bad++ < 5)
+                    fprintf(stderr, "checksum differs: len %u at %u skipword %u\n", l, o, sk);
             }
             free(buf);
         }

@@ -185,7 +185,10 @@ def test_parse_core_memory_safe_random_inputs(tmp_path, oracle):
     oracle built with AddressSanitizer + UBSan (tests/native/parse_fuzz): each
     frame alone in a heap block ending at its last 16-B load granule, three
     alignments, six parse modes, four staging variants — no out-of-bounds
-    access, no UB, and every record / FrameSlice equal to the oracle's."""
+    access, no UB, and every record / FrameSlice equal to the oracle's. The
+    same program runs the fix-up and checksum cores in place over every frame
+    (tests/fixup_sweep.py's corpus too): bytes, report and checksum equal the
+    oracle's, no store outside the frame."""
     import struct
     import subprocess
     here = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native")
@@ -195,6 +198,10 @@ def test_parse_core_memory_safe_random_inputs(tmp_path, oracle):
     base = ([bytes.fromhex(v["frame"]) for v in helpers.golden()["frames"]] + helpers.crafted_frames() +
             [oracle.gen_frame(abi.WL_IMIX, i) for i in range(200)])
     frames += base + helpers.mutate_frames(rng, base, 6000)
+    # the fix-up sweep's corpus, its 16 KiB .. 65535-B frames included: parse_fuzz also runs the
+    # fix-up and checksum cores (checksum_core.hpp) over every frame, in place, against the oracle
+    from tests import fixup_sweep
+    frames += list(fixup_sweep.corpus().frames)
     path = tmp_path / "frames.bin"
     path.write_bytes(b"".join(struct.pack("<I", len(f)) + f for f in frames))
     r = subprocess.run([os.path.join(here, "parse_fuzz"), str(path)], capture_output=True, text=True,

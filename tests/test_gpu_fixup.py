@@ -4,7 +4,12 @@ relations as fixed-point tests: a packet whose checksum field is rewritten by
 recompute_checksum (raw-buffer semantics) verifies under the packet API that
 parse uses (ipv4.rs:1073-1174, udp.rs:579-628, tcp.rs:1385-1428,
 icmp.rs:817-855, icmpv6.rs:527-600). Plus the 16M udp_ping SER batch checked
-in full through the parse path (configs[3] at its full size)."""
+in full through the parse path (configs[3] at its full size).
+
+Every batch here is offsets + lengths with 4-aligned frame starts and frames
+of at most 1514 B; tests/test_gpu_fixup_sweep.py (corpus: tests/fixup_sweep.py)
+covers the other table layouts, frames at odd addresses and every 16-B phase,
+payloads up to the 65535-B ceiling and the bytes around the frames."""
 import numpy as np
 import pytest
 
