@@ -1075,6 +1075,96 @@ static inline uint64_t nexg_flow_groups_workspace(uint64_t count) {
     return 16u + 8u * tiles + 8u * count + 8u * tp + 4u * ((count + 1u) & ~(uint64_t)1u);
 }
 
+/* The flow table: per-flow counters across batches. A table is an array of
+ * 64-byte entries in device memory, strictly ascending by `hash`, one entry
+ * per hash. The merge takes a table and the groups of one batch
+ * (nexg_flow_groups' rows, so strictly ascending by hash as well) and writes
+ * the new table: table_out = the union of table_in[0, n_in) and
+ * groups[0, n_groups) by hash, ascending. It is a pure function of its
+ * inputs: table_in is not changed, and a caller keeps two buffers and swaps
+ * them.
+ *
+ * A hash in both: the entry is table_in's with `packets` and `bytes`
+ * increased by the group's and last_epoch = epoch. MIXED is set when it was
+ * set already, or the group has mixed != 0 (its flags8 bit 0), or the
+ * group's key differs from the entry's (kind, proto, key): all 36 key bytes
+ * are compared, so an entry's padding must be zero, as the merge writes it.
+ * The group's key is the (kind, proto, key bytes) of frame `first_index`,
+ * recomputed from its record and frame bytes exactly as the groups pass
+ * recomputes keys, under `option`'s NEXG_FLOW_SYMMETRIC / NEXG_FLOW_NO_PORTS
+ * (the Toeplitz key plays no part). So MIXED is set if and only if two or
+ * more distinct keys have ever been counted under the hash; a collision is
+ * flagged, never silently merged, and the entry keeps the first key seen.
+ *
+ * A hash only in the groups: a new entry with the group's hash, packets and
+ * bytes, the recomputed key (kind, proto, the key bytes zero-padded to 36),
+ * MIXED from the group's flags8 bit 0, and last_epoch = epoch.
+ *
+ * A hash only in table_in: the entry is copied unchanged when
+ * last_epoch >= min_epoch and dropped otherwise (a plain unsigned compare,
+ * no wrap-around; min_epoch = 0 keeps everything). A matched entry is never
+ * dropped. This is the timeout: the caller picks what an epoch is (a batch
+ * number, seconds) and passes min_epoch = epoch - timeout.
+ *
+ * The group of frames without a flow (hash 0, kind NEXG_FLOW_NONE, empty key)
+ * is not special: it gets an entry like any other, and a real flow that
+ * hashes to 0 marks it MIXED.
+ *
+ * *out_count (device memory, 8-B aligned) = the size of the union, written
+ * even when it exceeds table_cap; rows at or past table_cap are not stored.
+ * out_slot (optional, n_groups entries, 4-B aligned): out_slot[j] = the
+ * position in the union of group j's entry, stored for every j whatever the
+ * capacity; with nexg_flow_groups' out_group it maps a frame to its entry.
+ *
+ * Caller memory: a first_index >= frames->count is a frame without a flow,
+ * and nothing is read for it (an empty frame table with such groups merges
+ * made-up rows). If table_in or groups are not ascending the result is
+ * unspecified, but even then every store stays inside
+ * table_out[0, table_cap), out_slot[0, n_groups) and *out_count, and nothing
+ * outside the arrays given, or outside a frame's own 16-B blocks, is read.
+ *
+ * A merge-path merge, without atomics (positions come from ranks and scans
+ * only, so a run repeats bit for bit). The merged order is by hash, a table
+ * entry before the group of the same hash. Per 256-position tile of that
+ * order one workgroup finds the tile's split of the two arrays by a binary
+ * search along its diagonal, stages the two runs' hashes in LDS, ranks each
+ * element against the other run there (which also tells whether its hash is
+ * in both), and scans the "leaves an entry" flags (a kept table entry, a
+ * group with a new hash); a one-workgroup scan of the tiles' totals gives
+ * every tile's first slot and *out_count; the write kernel builds each
+ * surviving position's entry and stores it with 16-byte stores.
+ * n_in == 0 && n_groups == 0 writes *out_count = 0 and launches nothing
+ * else. workspace: device memory (8-B aligned) of at least the table
+ * workspace helper's bytes. NEXG_EINVAL: unknown option flag bits,
+ * reserved != 0, a NULL or misaligned pointer (records / groups / table_in /
+ * table_out 16 B, out_count / workspace 8 B, out_slot 4 B), table_out
+ * overlapping table_in, n_in or n_groups above 2^31 - 1, an invalid frame
+ * table, a short workspace. Three kernels on `stream`. */
+#define NEXG_FLOW_ENTRY_MIXED 0x1u
+typedef struct nexg_flow_entry { /* 64 bytes, 16-B aligned */
+    uint32_t hash;
+    uint8_t kind, proto; /* of the recomputed key of the first frame ever seen under this hash */
+    uint8_t flags8;      /* bit 0 NEXG_FLOW_ENTRY_MIXED: more than one key has been seen under this hash */
+    uint8_t reserved;    /* 0 */
+    uint8_t key[36];     /* that key's bytes (0, 8, 12, 32 or 36 of them), zero-padded */
+    uint32_t last_epoch; /* `epoch` of the last merge that touched the entry */
+    uint64_t packets;
+    uint64_t bytes;
+} nexg_flow_entry;
+int nexg_flow_table_merge(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records,
+                          const nexg_flow_option* option /* as given to nexg_flow_batch; NULL = defaults */,
+                          const nexg_flow_group* groups, uint64_t n_groups, const nexg_flow_entry* table_in,
+                          uint64_t n_in, uint32_t epoch, uint32_t min_epoch, nexg_flow_entry* table_out,
+                          uint64_t table_cap, uint32_t* out_slot, uint64_t* out_count, void* workspace,
+                          uint64_t workspace_bytes, void* stream);
+/* per position of the merged order (n_in + n_groups of them) a u64, then a
+ * u32 per 256-position tile (padded to an even count) */
+static inline uint64_t nexg_flow_table_workspace(uint64_t n_in, uint64_t n_groups) {
+    const uint64_t n = n_in + n_groups;
+    const uint64_t tiles = (n + 255u) / 256u;
+    return 8u * n + 4u * ((tiles + 1u) & ~(uint64_t)1u);
+}
+
 /* ---- calibration (not a reference entry point) ---------------------------
  * The HBM stream ceilings the parse kernels are measured against, on the
  * caller's own buffer and box: `bytes` (a multiple of 16384) read with the

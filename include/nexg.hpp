@@ -34,6 +34,9 @@
  *   FlowGroup, Engine::flow_sort / flow_groups / flow_group_bufs
  *                           per-flow counters (an extension): the batch sorted
  *                           by flow hash and reduced to one row per flow
+ *   FlowEntry, Engine::flow_table_merge / flow_table_bufs
+ *                           the flow table across batches (an extension): a
+ *                           batch's flow rows merged into a table sorted by hash
  * The device does the parse and the checksums (nexg_parse_batch,
  * NEXG_OUT_RECORD) and the option lists (nexg_decode_options); this header
  * only reads header fields out of the frame bytes at the offsets the device
@@ -898,6 +901,7 @@ inline std::vector<uint8_t> message_bytes(const Icmpv6Packet& p) {
 /* ---- flow keys (extension: the reference has no flow notion) --------------- */
 
 using FlowGroup = nexg_flow_group;  // one row of Engine::flow_groups (include/nexg.h)
+using FlowEntry = nexg_flow_entry;  // one row of a flow table, Engine::flow_table_merge (include/nexg.h)
 
 // nexg_flow_option (include/nexg.h): which key a frame's flow row hashes.
 //   FlowOption().symmetric()        both directions of a conversation get one key
@@ -1438,6 +1442,74 @@ class Engine {  // one nexg context on one gfx950 device, one stream
         check_hip(hipMemcpyAsync(out.groups.data(), d_rows, g * 32, hipMemcpyDeviceToHost, stream_), "D2H");
         check_hip(hipMemcpyAsync(out.order.data(), d_order, n * 4, hipMemcpyDeviceToHost, stream_), "D2H");
         check_hip(hipMemcpyAsync(out.group_of.data(), d_group, n * 4, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        return out;
+    }
+
+    // The flow table across batches (nexg_flow_table_merge): table_out = the
+    // union by hash of table_in[0, n_in) and one batch's groups
+    // (flow_groups' rows), ascending. A hash in both adds the group's packets
+    // and bytes and sets last_epoch = epoch; a new hash makes an entry; an
+    // entry no group matches is dropped when last_epoch < min_epoch. All
+    // arrays are device memory (table_in, table_out and groups 16-B aligned,
+    // table_out apart from table_in); out_slot (may be null) receives the
+    // position of every group's entry. Returns the size of the union, which
+    // may exceed `cap` (one stream synchronisation).
+    uint64_t flow_table_merge(const nexg_frames& frames, const nexg_record* records, const FlowGroup* groups,
+                              uint64_t n_groups, const FlowEntry* table_in, uint64_t n_in, uint32_t epoch,
+                              uint32_t min_epoch, FlowEntry* table_out, uint64_t cap, uint32_t* out_slot,
+                              const FlowOption& option = {}) {
+        DeviceScope ds(device_);
+        const uint64_t wsb = nexg_flow_table_workspace(n_in, n_groups);
+        void* ws = scratch(40, wsb);
+        uint64_t* d_count = static_cast<uint64_t*>(scratch(37, 8));
+        check(nexg_flow_table_merge(ctx_, &frames, records, &option.get(), groups, n_groups, table_in, n_in, epoch,
+                                    min_epoch, table_out, cap, out_slot, d_count, ws, wsb, stream_),
+              "nexg_flow_table_merge");
+        uint64_t n = 0;
+        check_hip(hipMemcpyAsync(&n, d_count, 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        return n;
+    }
+
+    // parse (NEXG_OUT_RECORD) + flow + flow_sort + flow_groups of host frames,
+    // merged into a host copy of a flow table
+    struct FlowTableUpdate {
+        std::vector<FlowEntry> table;    // the new table, ascending by hash
+        std::vector<uint32_t> slot;      // per group of the batch: its entry's position
+        std::vector<uint32_t> group_of;  // per frame
+    };
+    FlowTableUpdate flow_table_bufs(const std::vector<FlowEntry>& table, const std::vector<std::vector<uint8_t>>& frames,
+                                    uint32_t epoch, uint32_t min_epoch = 0, const FlowOption& fopt = {},
+                                    ParseOption option = {}, ParseMode mode = ParseMode::Lenient) {
+        DeviceScope ds(device_);
+        const uint64_t n = frames.size(), n_in = table.size();
+        FlowTableUpdate out;
+        HostBatch hb(*this, frames);
+        nexg_record* d_recs = static_cast<nexg_record*>(scratch(3, n * 64));
+        nexg_flow* d_flows = static_cast<nexg_flow*>(scratch(34, n * 8));
+        uint32_t* d_order = static_cast<uint32_t*>(scratch(24, n * 4));
+        uint32_t* d_group = static_cast<uint32_t*>(scratch(38, n * 4));
+        FlowGroup* d_rows = static_cast<FlowGroup*>(scratch(39, n * 32));
+        FlowEntry* d_in = static_cast<FlowEntry*>(scratch(41, n_in * 64));
+        FlowEntry* d_out = static_cast<FlowEntry*>(scratch(42, (n_in + n) * 64));
+        uint32_t* d_slot = static_cast<uint32_t*>(scratch(43, n * 4));
+        uint64_t g = 0;
+        if (n) {
+            parse(hb.fb, option, mode, NEXG_OUT_RECORD, d_recs);
+            flow(hb.fb, d_recs, d_flows, fopt);
+            flow_sort(d_flows, n, d_order);
+            g = flow_groups(hb.fb, d_recs, d_flows, d_order, d_rows, n, d_group, fopt);
+        }
+        if (n_in) check_hip(hipMemcpyAsync(d_in, table.data(), n_in * 64, hipMemcpyHostToDevice, stream_), "H2D");
+        const uint64_t n_out = flow_table_merge(hb.fb, d_recs, d_rows, g, d_in, n_in, epoch, min_epoch, d_out, n_in + n,
+                                                d_slot, fopt);
+        out.table.resize(n_out);
+        out.slot.resize(g);
+        out.group_of.resize(n);
+        if (n_out) check_hip(hipMemcpyAsync(out.table.data(), d_out, n_out * 64, hipMemcpyDeviceToHost, stream_), "D2H");
+        if (g) check_hip(hipMemcpyAsync(out.slot.data(), d_slot, g * 4, hipMemcpyDeviceToHost, stream_), "D2H");
+        if (n) check_hip(hipMemcpyAsync(out.group_of.data(), d_group, n * 4, hipMemcpyDeviceToHost, stream_), "D2H");
         check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
         return out;
     }

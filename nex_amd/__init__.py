@@ -10,13 +10,13 @@ from .frame import (Frame, ParseError, ParseMode, ParseOption, frame_from_record
                     frame_view_payload)
 
 __all__ = ["abi", "Frame", "ParseError", "ParseMode", "ParseOption", "frame_from_record",
-           "frame_view_payload", "Engine", "FrameBatch", "NexgError"]
+           "frame_view_payload", "Engine", "FrameBatch", "FlowTable", "NexgError"]
 
 
 def __getattr__(name):
     # The engine needs libnexg.so (and torch); import it lazily so the pure
     # host mirror stays importable for CPU-only tooling.
-    if name in ("Engine", "FrameBatch", "NexgError"):
+    if name in ("Engine", "FrameBatch", "FlowTable", "NexgError"):
         from . import engine
         return getattr(engine, name)
     raise AttributeError(name)

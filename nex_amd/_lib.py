@@ -64,6 +64,8 @@ def load():
         "nexg_flow_sort": (I, [P, P, U64, P, P, U64, P]),
         "nexg_flow_groups": (I, [P, ctypes.POINTER(abi.Frames), P, P, ctypes.POINTER(abi.FlowOptionC), P, P, U64, P, P, P,
                                  U64, P]),
+        "nexg_flow_table_merge": (I, [P, ctypes.POINTER(abi.Frames), P, ctypes.POINTER(abi.FlowOptionC), P, U64, P, U64,
+                                      U32, U32, P, U64, P, P, P, U64, P]),
         "nexg_build_udp4_batch": (I, [P, ctypes.POINTER(abi.Udp4Build), P, U32, P]),
         "nexg_build_udp4_tuples": (I, [P, ctypes.POINTER(abi.Udp4Build), P, P, U32, P]),
         "nexg_build_udp6_batch": (I, [P, ctypes.POINTER(abi.Udp6Build), P, U32, P]),

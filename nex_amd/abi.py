@@ -527,11 +527,25 @@ def flow_groups_workspace(count):
     return 16 + 8 * tiles + 8 * count + 8 * ((tiles + 1) & ~1) + 4 * ((count + 1) & ~1)
 
 
+# the flow table across batches (nexg_flow_table_merge)
+FLOW_ENTRY_MIXED = 0x1  # nexg_flow_entry.flags8 bit 0: more than one key seen under the hash
+FLOW_ENTRY_DTYPE = np.dtype([("hash", "<u4"), ("kind", "u1"), ("proto", "u1"), ("flags8", "u1"), ("reserved", "u1"),
+                             ("key", "u1", (36,)), ("last_epoch", "<u4"), ("packets", "<u8"), ("bytes", "<u8")])
+assert FLOW_ENTRY_DTYPE.itemsize == 64
+
+
+def flow_table_workspace(n_in, n_groups):
+    """nexg_flow_table_workspace: bytes of nexg_flow_table_merge's workspace."""
+    n = int(n_in) + int(n_groups)
+    tiles = (n + 255) // 256
+    return 8 * n + 4 * ((tiles + 1) & ~1)
+
+
 #: static inline helpers of include/nexg.h (header-only, not exported)
 HEADER_INLINE = ("nexg_sparse_decode", "nexg_grouped_code", "nexg_grouped_exc_slot", "nexg_offsets32_bases",
                  "nexg_offsets32_bytes", "nexg_decap_select_workspace", "nexg_dns_tile_first_bytes",
                  "nexg_select_workspace", "nexg_gather_plan_workspace", "nexg_flow_partition_workspace",
-                 "nexg_flow_sort_workspace", "nexg_flow_groups_workspace")
+                 "nexg_flow_sort_workspace", "nexg_flow_groups_workspace", "nexg_flow_table_workspace")
 
 #: every symbol include/nexg.h declares (tests check the .so exports them)
 EXPORTED_SYMBOLS = (
@@ -540,6 +554,7 @@ EXPORTED_SYMBOLS = (
     "nexg_decap_batch", "nexg_decap_select", "nexg_dns_batch", "nexg_dns_entries",
     "nexg_filter_check", "nexg_select_batch", "nexg_gather_plan", "nexg_gather_frames", "nexg_gather_rows",
     "nexg_flow_batch", "nexg_flow_partition", "nexg_flow_sort", "nexg_flow_groups",
+    "nexg_flow_table_merge",
     "nexg_probe_span_clock", "nexg_probe_latency",
     "nexg_sparse_expand", "nexg_grouped_expand", "nexg_recompute_checksums_batch",
     "nexg_rx_config_default", "nexg_rx_open", "nexg_rx_next_batch", "nexg_rx_stats", "nexg_rx_close",

@@ -515,6 +515,40 @@ int nexg_flow_groups(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record
                                                   workspace, as_stream(stream)));
 }
 
+int nexg_flow_table_merge(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records,
+                          const nexg_flow_option* option, const nexg_flow_group* groups, uint64_t n_groups,
+                          const nexg_flow_entry* table_in, uint64_t n_in, uint32_t epoch, uint32_t min_epoch,
+                          nexg_flow_entry* table_out, uint64_t table_cap, uint32_t* out_slot, uint64_t* out_count,
+                          void* workspace, uint64_t workspace_bytes, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    uint32_t flags;
+    if (int rc = flow_option_flags(ctx, option, flags)) return rc;
+    if (n_in > 0x7FFFFFFFull || n_groups > 0x7FFFFFFFull)
+        return fail(ctx, NEXG_EINVAL, "flow_table: more than 2^31 - 1 entries or groups%s", nullptr);
+    if (!out_count) return fail(ctx, NEXG_EINVAL, "NULL out_count%s", nullptr);
+    const uint64_t n = n_in + n_groups;
+    if ((n_groups && (!groups || (frames->count && !records))) || (n_in && !table_in) || (table_cap && !table_out) ||
+        (n && !workspace))
+        return fail(ctx, NEXG_EINVAL, "NULL records, groups, table or workspace%s", nullptr);
+    if (int rc = check_workspace(ctx, "flow_table", n, workspace_bytes, nexg_flow_table_workspace(n_in, n_groups))) return rc;
+    if (misaligned(15u, records, groups, table_in, table_out) || misaligned(7u, out_count, workspace) ||
+        misaligned(3u, out_slot))
+        return fail(ctx, NEXG_EINVAL, "misaligned records, groups, table, output or workspace%s", nullptr);
+    // table_out[0, table_cap) against table_in[0, n_in), as addresses (a capacity that runs past the
+    // address space ends there)
+    const uint64_t in0 = reinterpret_cast<uint64_t>(table_in), out0 = reinterpret_cast<uint64_t>(table_out);
+    const uint64_t room = (~0ull - out0) / sizeof(nexg_flow_entry);
+    const uint64_t out1 = out0 + (table_cap < room ? table_cap : room) * sizeof(nexg_flow_entry);
+    if (n_in && table_cap && in0 < out1 && out0 < in0 + n_in * sizeof(nexg_flow_entry))
+        return fail(ctx, NEXG_EINVAL, "flow_table: table_out overlaps table_in%s", nullptr);
+    const nexg::ParseArgs a = to_args(frames);
+    DeviceGuard g(ctx);
+    return launched(ctx, nexg::launch_flow_table_merge(a, records, flags, groups, n_groups, table_in, n_in, epoch, min_epoch,
+                                                       table_out, table_cap, out_slot, out_count, workspace,
+                                                       as_stream(stream)));
+}
+
 int nexg_probe_stream(nexg_ctx* ctx, const void* data, uint64_t bytes, uint32_t out_per_64,
                       void* out, void* stream) {
     if (!ctx) return NEXG_EINVAL;

@@ -8,6 +8,8 @@
 // nexg_flow_sort is four such passes over the 32-bit hash with 256 buckets (a
 // stable LSD radix sort of (hash, index) pairs), and nexg_flow_groups reduces
 // the sorted batch to one row per run of equal hashes by prefix sums.
+// nexg_flow_table_merge keeps a table of flow entries across batches: a
+// merge-path merge of the table with a batch's groups, both ascending by hash.
 #include "table_kernels.hpp"
 #include "workspace_layout.hpp"
 
@@ -589,6 +591,211 @@ hipError_t launch_flow_groups(const ParseArgs& a, const nexg_record* recs, const
     if (rows)
         hipLaunchKernelGGL(k_group_rows, dim3((uint32_t)((rows + kTile - 1) / kTile)), b, 0, s, count, flows, order,
                            mark, tile_brk, tile_bytes, totals, starts, out_count, out, groups_cap);
+    return hipGetLastError();
+}
+
+// ---- table -------------------------------------------------------------------------------
+// The flow table across batches: table_out = the union of table_in and one
+// batch's groups, both ascending by hash (nexg_flow_table_merge, include/nexg.h).
+// A merge-path merge. The merged order is by hash, a table entry before the
+// group of the same hash. k_merge_mark, one workgroup per 256 positions of it:
+// two lanes find where the tile starts and ends in the two arrays (one binary
+// search along a diagonal each, the only dependent chains of global loads);
+// the two runs' hashes (256 in all) are staged in LDS; every element is ranked
+// against the other run there, which gives its position in the tile and whether
+// its hash is in both; the "leaves an entry" flags (a kept table entry, a group
+// with a new hash) are scanned in position order. k_tile_scan turns the tiles'
+// totals into their first slots and gives *out_count. k_merge_write, one lane
+// per position, builds the entry of a surviving position (table entry + group,
+// key recompute and compare) and stores it as four 16-B stores; a group
+// stores its entry's slot. No atomics.
+
+static_assert(sizeof(nexg_flow_entry) == 64, "nexg_flow_entry is 64 bytes (include/nexg.h)");
+static_assert(offsetof(nexg_flow_entry, kind) == 4 && offsetof(nexg_flow_entry, flags8) == 6 &&
+                  offsetof(nexg_flow_entry, key) == 8 && offsetof(nexg_flow_entry, last_epoch) == 44 &&
+                  offsetof(nexg_flow_entry, packets) == 48 && offsetof(nexg_flow_entry, bytes) == 56,
+              "the entry by dword: hash, kind | proto << 8 | flags8 << 16, 9 key dwords, last_epoch, packets, bytes");
+static_assert(offsetof(nexg_flow_group, flags8) == 6 && offsetof(nexg_flow_group, packets) == 12 &&
+                  offsetof(nexg_flow_group, bytes) == 16 && offsetof(nexg_flow_group, first_index) == 28,
+              "the group by dword: hash, kind | proto << 8 | flags8 << 16, first, packets, bytes, mixed, first_index");
+
+// what k_merge_mark leaves per position, in one u64: the source in the low
+// word (a table index, or a group index with kSrcGroup), in the high word the
+// exclusive in-tile prefix of the survivors (at most 255) and three flags
+constexpr uint32_t kSrcGroup = 1u << 31;
+constexpr uint32_t kAuxLive = 1u << 16;   // leaves an entry
+constexpr uint32_t kAuxBoth = 1u << 17;   // the hash is in the table and in the groups
+constexpr uint32_t kAuxValid = 1u << 18;  // some element took the position (always, with ascending inputs)
+
+constexpr uint32_t kEntryDw = sizeof(nexg_flow_entry) / 4u, kGroupDw = sizeof(nexg_flow_group) / 4u;
+
+// the number of table entries among the first d positions of the merged order:
+// the least i with A[i].hash > B[d - 1 - i].hash. lo <= i <= hi throughout, so
+// every index is inside its array whatever the arrays hold.
+__device__ __forceinline__ uint32_t merge_split(const nexg_flow_entry* A, uint32_t nA, const nexg_flow_group* B,
+                                                uint32_t nB, uint32_t d) {
+    uint32_t lo = d > nB ? d - nB : 0u, hi = d < nA ? d : nA;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2u;
+        const uint32_t ha = NEXG_GLOBAL(uint32_t, A)[(uint64_t)mid * kEntryDw];
+        const uint32_t hb = NEXG_GLOBAL(uint32_t, B)[(uint64_t)(d - 1u - mid) * kGroupDw];
+        if (ha <= hb)
+            lo = mid + 1u;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+// the number of s[0, n) below h (kIncl: at or below h), s ascending
+template <bool kIncl>
+__device__ __forceinline__ uint32_t lds_rank(const uint32_t* s, uint32_t n, uint32_t h) {
+    uint32_t lo = 0, len = n;
+    while (len) {
+        const uint32_t half = len / 2u, v = s[lo + half];
+        if (kIncl ? v <= h : v < h)
+            lo += half + 1u, len -= half + 1u;
+        else
+            len = half;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void k_merge_mark(const nexg_flow_entry* A, uint32_t nA, const nexg_flow_group* B,
+                                                    uint32_t nB, uint32_t min_epoch, uint64_t* mark,
+                                                    uint32_t* tile_first) {
+    __shared__ uint32_t s_ha[kTile], s_hb[kTile];  // the tile's table hashes and group hashes
+    __shared__ uint32_t s_src[kTile], s_aux[kTile];  // by position in the tile
+    __shared__ uint32_t s_split[2], s_edge[4], s_w[4];
+    const uint32_t t = threadIdx.x;
+    const uint64_t N = (uint64_t)nA + nB;
+    const uint32_t d0 = blockIdx.x * kTile;
+    const uint32_t cnt = N - d0 < kTile ? (uint32_t)(N - d0) : kTile;
+    if (t == 0u || t == 64u) s_split[t >> 6] = merge_split(A, nA, B, nB, d0 + (t ? cnt : 0u));
+    s_aux[t] = 0u;
+    __syncthreads();
+    // a0 <= min(d0, nA) and d0 - a0 <= nB by merge_split's bounds
+    const uint32_t a0 = s_split[0], b0 = d0 - a0;
+    uint32_t na = s_split[1] - a0;
+    // inputs that are not ascending can make the two searches disagree: any split with
+    // a0 + na <= nA and b0 + nb <= nB keeps the loads inside the arrays
+    if (na > cnt) na = nA - a0 < cnt ? nA - a0 : cnt;
+    const uint32_t nb = cnt - na;
+    // one element per lane: the tile's table entries, then its groups
+    const bool isA = t < na, isB = !isA && t < cnt;
+    uint32_t h = 0, last = 0;
+    if (isA) {
+        const auto* e = NEXG_GLOBAL(uint32_t, A) + (uint64_t)(a0 + t) * kEntryDw;
+        h = e[0], last = e[11];
+        s_ha[t] = h;
+    } else if (isB) {
+        h = NEXG_GLOBAL(uint32_t, B)[(uint64_t)(b0 + t - na) * kGroupDw];
+        s_hb[t - na] = h;
+    }
+    // the tie across a tile border: an entry that is the tile's last position has its
+    // group as the next tile's first, so the neighbours' hashes are looked at as well
+    if (t == 0u) {
+        const bool prev = a0 > 0u, next = b0 + nb < nB;
+        s_edge[0] = prev, s_edge[1] = prev ? NEXG_GLOBAL(uint32_t, A)[(uint64_t)(a0 - 1u) * kEntryDw] : 0u;
+        s_edge[2] = next, s_edge[3] = next ? NEXG_GLOBAL(uint32_t, B)[(uint64_t)(b0 + nb) * kGroupDw] : 0u;
+    }
+    __syncthreads();
+    if (isA) {
+        const uint32_t r = lds_rank<false>(s_hb, nb, h);  // groups below: the entry goes before its group
+        const bool both = r < nb ? s_hb[r] == h : (s_edge[2] != 0u && s_edge[3] == h);
+        const bool live = both || last >= min_epoch;
+        s_src[t + r] = a0 + t;  // t + r < na + nb
+        s_aux[t + r] = kAuxValid | (live ? kAuxLive : 0u) | (both ? kAuxBoth : 0u);
+    } else if (isB) {
+        const uint32_t j = t - na, r = lds_rank<true>(s_ha, na, h);  // entries at or below
+        const bool both = r > 0u ? s_ha[r - 1u] == h : (s_edge[0] != 0u && s_edge[1] == h);
+        s_src[j + r] = kSrcGroup | (b0 + j);
+        s_aux[j + r] = kAuxValid | (both ? kAuxBoth : kAuxLive);
+    }
+    __syncthreads();
+    const uint32_t aux = s_aux[t];
+    uint32_t total;
+    const uint32_t before = block_excl_scan((aux & kAuxLive) ? 1u : 0u, s_w, total);
+    if (t < cnt) mark[(uint64_t)d0 + t] = (uint64_t)(aux | before) << 32 | ((aux & kAuxValid) ? s_src[t] : 0u);
+    if (t == 0u) tile_first[blockIdx.x] = total;
+}
+
+// Every index out of the workspace (caller memory) is checked against its
+// array before it is used, and the slot against `cap`.
+__global__ __launch_bounds__(256) void k_merge_write(ParseArgs a, const nexg_record* recs, uint32_t opt,
+                                                     const nexg_flow_entry* A, uint32_t nA, const nexg_flow_group* B,
+                                                     uint32_t nB, uint32_t epoch, const uint64_t* mark,
+                                                     const uint32_t* tile_first, nexg_flow_entry* out, uint64_t cap,
+                                                     uint32_t* out_slot) {
+    const uint64_t N = (uint64_t)nA + nB, p = (uint64_t)blockIdx.x * kTile + threadIdx.x;
+    const uint64_t m = p < N ? mark[p] : 0ull;
+    const uint32_t src = (uint32_t)m, aux = (uint32_t)(m >> 32), idx = src & ~kSrcGroup;
+    const bool valid = (aux & kAuxValid) != 0u, both = (aux & kAuxBoth) != 0u;
+    const bool fromB = valid && (src & kSrcGroup) != 0u && idx < nB, fromA = valid && !(src & kSrcGroup) && idx < nA;
+    uint64_t slot = (uint64_t)tile_first[blockIdx.x] + (aux & 0xFFFFu);
+    if (fromB) {
+        if (both) slot -= 1u;  // its entry is the position before, which survives
+        if (out_slot) out_slot[idx] = (uint32_t)slot;
+    }
+    const bool store = (fromA || fromB) && (aux & kAuxLive) != 0u && slot < cap;
+    // the group of a matched entry is the next position: entry `idx` at position p has p - idx groups before it
+    const uint32_t gi = fromB ? idx : (uint32_t)(p - idx);
+    const bool with_group = store && (fromB || (both && p >= idx && p - idx < nB));
+    uint4 g0 = make_uint4(0u, 0u, 0u, 0u), g1 = g0;
+    if (with_group) {
+        g0 = load16(reinterpret_cast<const uint8_t*>(B + gi));
+        g1 = load16(reinterpret_cast<const uint8_t*>(B + gi) + 16u);
+    }
+    bool ext;
+    uint64_t l64;
+    const uint32_t fi = g1.w;
+    const FlowKeyWords kw = flow_key_words(a, recs, fi, with_group && fi < a.count, opt, ext, l64);
+    uint32_t K[9];
+#pragma unroll
+    for (uint32_t j = 0; j < 9; j++) K[j] = __builtin_bswap32(kw.W[j]);  // the key bytes in memory order
+    const uint32_t tag = kw.kind | kw.proto << 8;
+    uint4 e0, e1, e2, e3;
+    if (fromB) {
+        e0 = make_uint4(g0.x, tag | (g0.y & (NEXG_FLOW_ENTRY_MIXED << 16)), K[0], K[1]);
+        e1 = make_uint4(K[2], K[3], K[4], K[5]);
+        e2 = make_uint4(K[6], K[7], K[8], epoch);
+        e3 = make_uint4(g0.w, 0u, g1.x, g1.y);
+    } else {
+        e0 = e1 = e2 = e3 = make_uint4(0u, 0u, 0u, 0u);
+        if (store) {
+            const uint8_t* e = reinterpret_cast<const uint8_t*>(A + idx);
+            e0 = load16(e), e1 = load16(e + 16u), e2 = load16(e + 32u), e3 = load16(e + 48u);
+        }
+        if (with_group) {
+            const uint32_t differ = ((e0.y ^ tag) & 0xFFFFu) | (e0.z ^ K[0]) | (e0.w ^ K[1]) | (e1.x ^ K[2]) | (e1.y ^ K[3]) |
+                                    (e1.z ^ K[4]) | (e1.w ^ K[5]) | (e2.x ^ K[6]) | (e2.y ^ K[7]) | (e2.z ^ K[8]);
+            e0.y |= (g0.y & (NEXG_FLOW_ENTRY_MIXED << 16)) | (differ ? NEXG_FLOW_ENTRY_MIXED << 16 : 0u);
+            e2.w = epoch;
+            const uint64_t packets = ((uint64_t)e3.y << 32 | e3.x) + g0.w;
+            const uint64_t bytes = ((uint64_t)e3.w << 32 | e3.z) + ((uint64_t)g1.y << 32 | g1.x);
+            e3 = make_uint4((uint32_t)packets, (uint32_t)(packets >> 32), (uint32_t)bytes, (uint32_t)(bytes >> 32));
+        }
+    }
+    if (store) {
+        uint4* o = reinterpret_cast<uint4*>(out + slot);
+        o[0] = e0, o[1] = e1, o[2] = e2, o[3] = e3;
+    }
+}
+
+hipError_t launch_flow_table_merge(const ParseArgs& a, const nexg_record* recs, uint32_t opt, const nexg_flow_group* groups,
+                                   uint64_t n_groups, const nexg_flow_entry* table_in, uint64_t n_in, uint32_t epoch,
+                                   uint32_t min_epoch, nexg_flow_entry* table_out, uint64_t table_cap, uint32_t* out_slot,
+                                   uint64_t* out_count, void* workspace, hipStream_t s) {
+    if (n_in + n_groups == 0) return hipMemsetAsync(out_count, 0, 8, s);
+    const FlowTableLayout w = FlowTableLayout::from(n_in, n_groups);
+    uint64_t* mark = region<uint64_t>(workspace, w.mark);
+    uint32_t* tile_first = region<uint32_t>(workspace, w.tile_first);
+    const dim3 gT((uint32_t)w.tiles), b(kTile);
+    hipLaunchKernelGGL(k_merge_mark, gT, b, 0, s, table_in, (uint32_t)n_in, groups, (uint32_t)n_groups, min_epoch, mark,
+                       tile_first);
+    hipLaunchKernelGGL(k_tile_scan<uint32_t>, dim3(1), b, 0, s, tile_first, w.tiles, out_count);
+    hipLaunchKernelGGL(k_merge_write, gT, b, 0, s, a, recs, opt, table_in, (uint32_t)n_in, groups, (uint32_t)n_groups, epoch,
+                       mark, tile_first, table_out, table_cap, out_slot);
     return hipGetLastError();
 }
 

@@ -161,6 +161,12 @@ hipError_t launch_flow_sort(const nexg_flow* flows, uint64_t count, uint32_t* ou
 hipError_t launch_flow_groups(const ParseArgs& a, const nexg_record* recs, const nexg_flow* flows, uint32_t opt,
                               const uint32_t* order, nexg_flow_group* out, uint64_t groups_cap, uint32_t* out_group,
                               uint64_t* out_count, void* workspace, hipStream_t s);
+// nexg_flow_table_merge (nexg_flow.hip); the workspace as nexg_flow_table_workspace lays it out.
+// n_in and n_groups are below 2^31.
+hipError_t launch_flow_table_merge(const ParseArgs& a, const nexg_record* recs, uint32_t opt, const nexg_flow_group* groups,
+                                   uint64_t n_groups, const nexg_flow_entry* table_in, uint64_t n_in, uint32_t epoch,
+                                   uint32_t min_epoch, nexg_flow_entry* table_out, uint64_t table_cap, uint32_t* out_slot,
+                                   uint64_t* out_count, void* workspace, hipStream_t s);
 
 hipError_t launch_probe_stream(const uint8_t* data, uint64_t tiles, uint32_t mode, void* out, hipStream_t s);
 hipError_t launch_probe_latency(uint32_t* buf, uint32_t lines, uint32_t start, uint32_t steps, uint32_t loaded_wgs,

@@ -4,7 +4,9 @@
 // header other people compile); the structs here name the regions inside and
 // give their byte offsets, and the launchers of nexg_flow.hip take every
 // pointer from them. tests/native/workspace_layout_test.cpp holds the two
-// against each other: equal sizes, regions aligned, disjoint and in bounds.
+// against each other: equal sizes, regions aligned, disjoint and in bounds
+// (FlowTableLayout: tests/test_flow_table_layout.py, through
+// tests/native/cpp_flow_table_test.cpp).
 // Plain host code: <stdint.h> and nexg.h only.
 #pragma once
 #include <stdint.h>
@@ -77,6 +79,25 @@ struct FlowGroupsLayout {
         w.tile_brk = w.tile_heads + 4u * even_tiles;
         w.starts = w.tile_brk + 4u * even_tiles;
         w.bytes = w.starts + 4u * ((count + 1u) & ~(uint64_t)1u);
+        return w;
+    }
+};
+
+// nexg_flow_table_workspace: a u64 per position of the merged order, then a
+// u32 per 256-position tile (an even number of slots)
+struct FlowTableLayout {
+    uint64_t positions;   // n_in + n_groups
+    uint64_t tiles;       // of 256 merged positions
+    uint64_t mark;        // u64[positions]
+    uint64_t tile_first;  // u32[tiles]
+    uint64_t bytes;
+    static FlowTableLayout from(uint64_t n_in, uint64_t n_groups) {
+        FlowTableLayout w;
+        w.positions = n_in + n_groups;
+        w.tiles = (w.positions + 255u) / 256u;
+        w.mark = 0;
+        w.tile_first = 8u * w.positions;
+        w.bytes = w.tile_first + 4u * ((w.tiles + 1u) & ~(uint64_t)1u);
         return w;
     }
 };

@@ -579,6 +579,50 @@ class Engine:
             run(groups, n, None)
         return groups[: n * 32], group_of[:count], n, order
 
+    def flow_table_merge(self, batch: FrameBatch, records, groups, table=None, epoch=0, min_epoch=0, option=None,
+                         table_cap=None, out=None, stream=None):
+        """Merge one batch's groups into a flow table (nexg_flow_table_merge):
+        the union by hash of `table` and `groups`, ascending. `groups` is the
+        uint8 device tensor Engine.flow_groups returned for `batch` (whole
+        nexg_flow_group rows), `records` the batch's records, `option` the
+        FlowOption given to Engine.flow, `table` a uint8 device tensor holding
+        nexg_flow_entry rows (abi.FLOW_ENTRY_DTYPE) ascending by hash, or
+        None for an empty table; it is not changed. A hash in both adds the
+        group's packets and bytes to the entry and sets last_epoch = epoch; a
+        new hash makes an entry; an entry no group matches is dropped when
+        last_epoch < min_epoch. MIXED (flags8 bit 0) marks an entry under
+        which more than one flow key has been counted.
+
+        Returns (table_out, n_out, slot): the new table as a uint8 device
+        tensor of min(n_out, table_cap) entries, written into `out` when
+        given (a uint8 device tensor of table_cap entries that does not
+        overlap `table`), n_out the size of the union (an int: one
+        synchronisation of the stream; it may exceed table_cap, whose default
+        is room for every entry and group), slot an int32 device tensor with
+        the position in the union of every group's entry."""
+        from .flow import FlowOption
+        torch = _torch()
+        fo = (option if option is not None else FlowOption()).to_c()  # ValueError for what the merge rejects
+        dev = self.torch_device
+        n_groups = groups.numel() * groups.element_size() // 32
+        n_in = 0 if table is None else table.numel() * table.element_size() // 64
+        cap = n_in + n_groups if table_cap is None else int(table_cap)
+        if out is None:
+            out = torch.empty(max(cap, 1) * 64, dtype=torch.uint8, device=dev)
+        elif out.numel() * out.element_size() < cap * 64:
+            raise ValueError(f"out holds {out.numel() * out.element_size()} B; {cap} entries need {cap * 64} B")
+        slot = torch.empty(max(n_groups, 1), dtype=torch.int32, device=dev)
+        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
+        ws_bytes = abi.flow_table_workspace(n_in, n_groups)
+        ws = self._workspace(ws_bytes)
+        self._check(self.lib.nexg_flow_table_merge(self.ctx, _frames(batch), _ptr(records), ctypes.byref(fo),
+                                                   _ptr(groups) if n_groups else None, n_groups,
+                                                   _ptr(table) if n_in else None, n_in, int(epoch), int(min_epoch),
+                                                   _ptr(out), cap, _ptr(slot), _ptr(cnt), _ptr(ws), ws_bytes,
+                                                   self._stream(stream)))
+        n_out = int(cnt.item())  # waits for the kernels
+        return out[: min(n_out, cap) * 64], n_out, slot[:n_groups]
+
     def dns(self, batch: FrameBatch, records, port: int = abi.DNS_PORT, any_udp: bool = False, entries_cap=None,
             stream=None):
         """Walk every DNS message of `batch` in place (nexg_dns_batch +
@@ -986,3 +1030,63 @@ class Engine:
         self._check(self.lib.nexg_gen_udp4_params(self.ctx, seed, first_index, count,
                                                   *[_ptr(t) for t in t32 + t16], self._stream(stream)))
         return [t[:count] for t in t32 + t16]
+
+
+class FlowTable:
+    """Per-flow counters across batches: a flow table kept in device memory
+    (nexg_flow_entry rows, abi.FLOW_ENTRY_DTYPE, ascending by hash) in two
+    buffers that swap at every update.
+
+        table = FlowTable(eng, FlowOption(symmetric=True))
+        for epoch, batch in enumerate(batches):
+            rec = eng.parse(batch, out_kind=abi.OUT_RECORD)
+            slot, group_of = table.update(batch, rec, epoch, min_epoch=max(epoch - 30, 0))
+        rows = table.rows()
+    """
+
+    def __init__(self, engine: Engine, option=None, capacity: int = 1 << 16):
+        self.engine = engine
+        self.option = option
+        self.capacity = max(int(capacity), 1)
+        self.count = 0
+        self._cur = self._buffer()
+        self._next = self._buffer()
+
+    def _buffer(self):
+        return _torch().empty(self.capacity * 64, dtype=_torch().uint8, device=self.engine.torch_device)
+
+    def update(self, batch: FrameBatch, records, epoch: int, min_epoch: int = 0, stream=None):
+        """Count `batch` into the table: flow rows, sort, groups, merge
+        (Engine.flow / flow_groups / flow_table_merge), then the buffers swap.
+        `records` is the batch's NEXG_OUT_RECORD parse. Entries that no group
+        of the batch matched and whose last_epoch is below min_epoch are
+        dropped. When the new table does not fit, the capacity doubles until
+        it does and the merge alone runs again (it is a pure function of its
+        inputs). Returns (slot, group_of): int32 device tensors with the
+        table position of every group's entry and the group of every frame,
+        so frame i's entry is row slot[group_of[i]] of the new table."""
+        eng = self.engine
+        flows = eng.flow(batch, records, self.option, stream)
+        groups, group_of, _, _ = eng.flow_groups(batch, records, flows, self.option, stream=stream)
+        table = self._cur[: self.count * 64]
+        while True:
+            if self._next.numel() < self.capacity * 64:
+                self._next = self._buffer()
+            _, n_out, slot = eng.flow_table_merge(batch, records, groups, table, epoch, min_epoch, self.option,
+                                                  table_cap=self.capacity, out=self._next, stream=stream)
+            if n_out <= self.capacity:
+                break
+            while self.capacity < n_out:
+                self.capacity *= 2
+        self._cur, self._next = self._next, self._cur
+        self.count = n_out
+        return slot, group_of
+
+    def device_rows(self):
+        """The table as a uint8 device tensor of `count` entries (a view of
+        the current buffer: the update after next overwrites it)."""
+        return self._cur[: self.count * 64]
+
+    def rows(self):
+        """The table on the host: an abi.FLOW_ENTRY_DTYPE array."""
+        return self.device_rows().cpu().numpy().view(abi.FLOW_ENTRY_DTYPE).copy()

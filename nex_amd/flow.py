@@ -1,14 +1,16 @@
-"""Flow keys, the Toeplitz RSS hash, the flow-affine partition and the
-per-flow counters (nexg_flow_batch / nexg_flow_partition / nexg_flow_sort /
-nexg_flow_groups, include/nexg.h; an extension: the reference has no flow
-notion).
+"""Flow keys, the Toeplitz RSS hash, the flow-affine partition, the per-flow
+counters and the flow table across batches (nexg_flow_batch /
+nexg_flow_partition / nexg_flow_sort / nexg_flow_groups /
+nexg_flow_table_merge, include/nexg.h; an extension: the reference has no
+flow notion).
 
 FlowOption is the host form of struct nexg_flow_option. toeplitz, flow_host,
-partition_host, sort_host and groups_host restate the header's specification
-in plain Python: the GPU kernels are tested against them, and they are
-themselves pinned by the published RSS verification vectors
-(tests/golden/flow_vectors.json) and an independent group-by
-(tests/test_flow_groups_host.py)."""
+partition_host, sort_host, groups_host and merge_host restate the header's
+specification in plain Python: the GPU kernels are tested against them, and
+they are themselves pinned by the published RSS verification vectors
+(tests/golden/flow_vectors.json), an independent group-by
+(tests/test_flow_groups_host.py) and an independent per-hash dictionary fed
+frame by frame (tests/test_flow_table_host.py)."""
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
 
@@ -190,3 +192,73 @@ def groups_host(frames: Sequence[Optional[bytes]], records, lengths: Sequence[in
         out[g] = (r["hash"], r["kind"], r["proto"], abi.FLOW_GROUP_MIXED if r["mixed"] else 0, 0, r["first"], r["packets"],
                   r["bytes"], r["mixed"], r["first_index"])
     return out, group_of, len(rows)
+
+
+def merge_host(table, groups, frames: Sequence[Optional[bytes]], records, lengths: Sequence[int],
+               option: FlowOption = FlowOption(), epoch: int = 0, min_epoch: int = 0):
+    """nexg_flow_table_merge on the host: (table_out, slot). `table` is an
+    abi.FLOW_ENTRY_DTYPE array strictly ascending by hash, `groups` the
+    abi.FLOW_GROUP_DTYPE rows of one batch (groups_host's, strictly ascending
+    by hash), frames / records / lengths that batch as flows_host takes it.
+    table_out is their union by hash, ascending, slot (u32 [n_groups]) the
+    position of every group's entry in it.
+
+    A hash in both keeps the table's entry, adds the group's packets and
+    bytes, sets last_epoch = epoch, and sets MIXED when it was set, when the
+    group's flags8 bit 0 is set, or when the group's key (kind, proto, the 36
+    zero-padded key bytes of frame first_index; a first_index past the batch
+    is a frame without a flow) differs from the entry's. A hash only in the
+    groups makes an entry of the group with that key. A hash only in the table
+    is kept when last_epoch >= min_epoch and dropped otherwise."""
+    table = np.asarray(table).view(abi.FLOW_ENTRY_DTYPE).reshape(-1)
+    groups = np.asarray(groups).view(abi.FLOW_GROUP_DTYPE).reshape(-1)
+    count = len(frames)
+
+    def group_key(g):
+        i = int(g["first_index"])
+        kind, proto, key = abi.FLOW_NONE, 0, b""
+        if i < count:
+            kind, proto, _, key = flow_key(frames[i], records[i], int(lengths[i]), option)
+        return kind, proto, np.frombuffer(bytes(key).ljust(36, b"\0"), np.uint8)
+
+    out = []
+    slot = np.zeros(len(groups), np.uint32)
+    i = j = n_out = 0
+    while i < len(table) or j < len(groups):
+        # ties: the table's entry comes first and takes its group with it
+        if j == len(groups) or (i < len(table) and int(table[i]["hash"]) <= int(groups[j]["hash"])):
+            e = table[i].copy()
+            i += 1
+            matched = j < len(groups) and int(groups[j]["hash"]) == int(e["hash"])
+            if matched:
+                g = groups[j]
+                kind, proto, key = group_key(g)
+                differs = kind != int(e["kind"]) or proto != int(e["proto"]) or not (key == e["key"]).all()
+                mixed = bool(int(e["flags8"]) & abi.FLOW_ENTRY_MIXED) or \
+                    bool(int(g["flags8"]) & abi.FLOW_GROUP_MIXED) or differs
+                e["flags8"] = (int(e["flags8"]) & ~abi.FLOW_ENTRY_MIXED) | (abi.FLOW_ENTRY_MIXED if mixed else 0)
+                e["packets"] += np.uint64(g["packets"])
+                e["bytes"] += np.uint64(g["bytes"])
+                e["last_epoch"] = epoch
+                slot[j] = n_out
+                j += 1
+            keep = matched or int(e["last_epoch"]) >= min_epoch
+            if keep:
+                out.append(e)
+            n_out += 1 if keep else 0
+        else:
+            g = groups[j]
+            kind, proto, key = group_key(g)
+            e = np.zeros(1, abi.FLOW_ENTRY_DTYPE)[0]
+            e["hash"], e["kind"], e["proto"] = g["hash"], kind, proto
+            e["flags8"] = int(g["flags8"]) & abi.FLOW_GROUP_MIXED
+            e["key"] = key
+            e["last_epoch"], e["packets"], e["bytes"] = epoch, g["packets"], g["bytes"]
+            slot[j] = n_out
+            out.append(e)
+            n_out += 1
+            j += 1
+    res = np.zeros(len(out), abi.FLOW_ENTRY_DTYPE)
+    for k, e in enumerate(out):
+        res[k] = e
+    return res, slot
