@@ -36,6 +36,10 @@ def lib():
         L.harness_checksum.argtypes = [P, U64, P, P, U32, U64, U32, P, U32, P]
         L.harness_span_declined.restype = None
         L.harness_span_declined.argtypes = [P]
+        L.harness_span_stats.restype = ctypes.POINTER(U64)
+        L.harness_span_stats.argtypes = []
+        L.harness_span_stats_reset.restype = None
+        L.harness_span_stats_reset.argtypes = []
         _lib = L
     return _lib
 
@@ -122,6 +126,26 @@ def span_groups(data, offsets, flags=0, ip_offset=0, declined=None):
         lib().harness_span_declined(ctypes.c_void_p(None))
     assert rc == 0, f"harness_span_groups: {rc}"
     return recs
+
+
+SPAN_STATS = ("declined", "declined_past_80", "deferred", "groups_with_declined", "hbm_byte_loads", "hbm_range_sums")
+
+
+def span_group_stats(data, offsets, flags=0, ip_offset=0):
+    """harness_span_stats of every 256-frame group of a packed batch on its
+    own: [(records, declined uint8[frames of the group], {SPAN_STATS name:
+    count})], what k_parse_span's generic section does for that group."""
+    data = np.ascontiguousarray(data, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    out = []
+    for g0 in range(0, len(offs) - 1, 256):
+        go = offs[g0: g0 + 257]
+        declined = np.zeros(len(go) - 1, np.uint8)
+        lib().harness_span_stats_reset()
+        recs = span_groups(data, go, flags, ip_offset, declined=declined)
+        st = lib().harness_span_stats()
+        out.append((recs, declined, {n: int(st[i]) for i, n in enumerate(SPAN_STATS)}))
+    return out
 
 
 def _table(data, offsets, lengths, stride, offsets32, bases):

@@ -2,12 +2,15 @@
 lengths array, or a stride the tile kernels do not take) against the oracle's
 batch parser on the very same layout (oracle/nex_oracle.c nexo_parse_batch).
 
-The span kernel streams each 256-frame group's bytes through 16-KiB LDS
-sub-tiles and derives L4 sums from chunk prefix sums, so the cases here aim at
-its edges: frames crossing sub-tile edges, frames far longer than a sub-tile
-(up to the 65535-B ceiling), odd frame starts (the batch base itself is 4-B
-aligned, nexg.h), groups with a frame the layout rejects (BAD_EXTENT ->
-per-frame fallback), partial last groups."""
+The span kernel streams each 256-frame group's bytes through LDS sub-tiles
+(16 KiB for records, 24 KiB for the other output kinds) and derives L4 sums
+from chunk prefix sums, so the shuffled mixes here carry frames crossing
+sub-tile edges, frames far longer than a sub-tile (up to the 65535-B ceiling),
+odd frame starts (the batch base itself is 4-B aligned, nexg.h), groups with a
+frame the layout rejects (BAD_EXTENT -> per-frame fallback), partial last
+groups. Where a frame lands against an edge is the shuffle's to say: every
+exact position of a head, an end and a group end against an edge is placed by
+tests/test_gpu_span_geometry.py."""
 import numpy as np
 import pytest
 

@@ -141,7 +141,9 @@ def test_unaligned_frames_take_fast_path_bit_exact(engine, oracle, out_kind):
     """Canonical IMIX frames at every byte alignment (0-3 byte gaps, offsets +
     lengths + monotone hint -> span kernel; without the hint -> two-pass), a
     share with a corrupted payload byte so both checksum verdicts occur, and
-    windows straddling 16-KiB sub-tile edges: records equal the oracle's."""
+    windows that straddle sub-tile edges (16 KiB for records, 24 KiB for the
+    sparse output) wherever the random gaps put them; every exact position is
+    placed by tests/test_gpu_span_geometry.py: records equal the oracle's."""
     import torch
     rng = np.random.default_rng(99)
     frames = [bytearray(oracle.gen_frame(abi.WL_IMIX, i)) for i in range(30000)]
