@@ -875,6 +875,107 @@ int nexg_gather_frames(nexg_ctx* ctx, const nexg_frames* sel, const uint64_t* ou
 int nexg_gather_rows(nexg_ctx* ctx, const void* rows, uint32_t row_bytes, uint64_t rows_count,
                      const uint32_t* index, uint64_t n, void* out, void* stream);
 
+/* ---- fixed-string match on frame bytes (extension) -----------------------------
+ * The reference has no payload search; like the selection above this is an
+ * extension, and the text below is its whole specification
+ * (nex_amd/match.py match_host / match_rows_host / match_select_host restate
+ * it on the host). nexg_match_batch looks for up to 32 byte strings of 1..16
+ * bytes in every frame's payload (or in the whole frame) and gives a row per
+ * frame; nexg_match_select compacts the frame table by the rows' masks into
+ * the kind of table nexg_select_batch writes, which parse, decap, dns, flow,
+ * the gather calls and nexg_match_batch itself take as it stands.
+ *
+ * The region of frame i. With NEXG_MATCH_FRAME it is [0, len(i)): `records`
+ * may be NULL and is not read. Otherwise it is [payload_off, payload_off +
+ * payload_len) of records[i], when the record's status is 0, payload_len > 0
+ * and payload_off + payload_len <= len(i). Every other frame has an empty
+ * region: an error status, a record that points past its frame, and under
+ * either flag an extent that leaves [0, data_bytes) or a length above 65535.
+ * A frame with an empty region gets the row {0, 0, NEXG_PAT_NONE, 0}.
+ *
+ * Pattern p occurs at region-relative position q, in a region of n bytes,
+ * when q + len_p <= n, off_lo <= q <= off_hi, and region[q + k] == bytes[k]
+ * for every k < len_p; under NEXG_PAT_NOCASE both sides first map the bytes
+ * 0x41..0x5A to themselves | 0x20 and nothing else (0x40, 0x5B, 0x60, 0x7B
+ * and bytes from 0x80 up stay as they are). Occurrences may overlap; the
+ * position window bounds the start only: off_lo = off_hi = 0 is "starts
+ * with", 0..65535 "anywhere".
+ *
+ * Records are caller memory: nothing outside a frame's own extent is read
+ * (the 16-B block rule of the frame batch layout applies). In a packed batch
+ * a pattern that only the next frame's first bytes would complete, or one
+ * that begins in the header bytes before payload_off, does not occur.
+ *
+ * NEXG_EINVAL for a set (nexg_patterns_check tells): n_patterns 0 or above
+ * 32, a len of 0 or above 16, nonzero bytes past len, unknown flag bits of a
+ * pattern or of the set, nonzero reserved bytes, off_lo > off_hi. */
+#define NEXG_MATCH_MAX_PATTERNS 32
+#define NEXG_MATCH_MAX_LEN 16
+#define NEXG_PAT_NOCASE 0x1u  /* per pattern: ASCII letters compare case-insensitively */
+#define NEXG_MATCH_FRAME 0x1u /* per set: the region is the whole frame; default: Frame.payload */
+#define NEXG_PAT_NONE 0xFFu   /* first_pat of a row whose mask is 0 */
+typedef struct nexg_pattern { /* 32 bytes */
+    uint8_t bytes[16];        /* the first `len` are compared; the rest must be 0 */
+    uint8_t len;              /* 1..16 */
+    uint8_t flags;            /* NEXG_PAT_*; unknown bits -> NEXG_EINVAL */
+    uint16_t off_lo, off_hi;  /* the occurrence starts at a region-relative position in [off_lo, off_hi] */
+    uint8_t reserved[10];     /* must be 0 */
+} nexg_pattern;
+typedef struct nexg_patterns { /* host memory; read during the call, not after it; 1032 bytes */
+    uint32_t n_patterns;       /* 1..32 */
+    uint32_t flags;            /* NEXG_MATCH_*; unknown bits -> NEXG_EINVAL */
+    nexg_pattern pat[NEXG_MATCH_MAX_PATTERNS];
+} nexg_patterns;
+typedef struct nexg_match { /* 8 bytes per frame */
+    uint32_t mask;          /* bit p: pattern p occurs in the region */
+    uint16_t first_off;     /* FRAME-relative offset of the earliest occurrence of any pattern; 0 if mask == 0 */
+    uint8_t first_pat;      /* the lowest pattern index among those occurring at first_off; NEXG_PAT_NONE if mask == 0 */
+    uint8_t reserved;       /* 0 */
+} nexg_match;
+
+/* NEXG_OK when nexg_match_batch would accept the set, else NEXG_EINVAL.
+ * Host only: no context, no device. */
+int nexg_patterns_check(const nexg_patterns* set);
+
+/* out[i] = frame i's row. records[i] = frame i's record (16-B aligned; under
+ * NEXG_MATCH_FRAME any pointer, NULL too: it is not read); out: 8-B aligned,
+ * `count` entries; count must not exceed 2^32 - 1. count == 0 launches
+ * nothing. A row is the OR of its occurrences' bits and the minimum of their
+ * (first_off << 8 | pattern) keys, gathered with workgroup-local (LDS) atomics
+ * whose result does not depend on the order of arrival: a run repeats bit for
+ * bit. NEXG_EINVAL: an invalid set or frame table, NULL or misaligned records
+ * without NEXG_MATCH_FRAME, a NULL or misaligned out. One kernel on `stream`. */
+int nexg_match_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records,
+                     const nexg_patterns* set, nexg_match* out, void* stream);
+
+/* Order-preserving selection by the rows. matches[i] (8-B aligned) = frame
+ * i's row; frame i is selected when
+ *   (any_mask == 0 || (mask & any_mask) != 0) && (mask & all_mask) == all_mask
+ *   && (mask & none_mask) == 0
+ * so all-zero masks select every frame. For the k-th selected frame in index
+ * order out_index[k] = i, out_off[k] = off(i), out_len[k] = len(i) exactly as
+ * the input table defines them for any layout (a length above 2^32 - 1 is
+ * stored as 2^32 - 1); *out_count (device memory, 8-B aligned) = the number
+ * selected. {frames->data, frames->data_bytes, out_off, out_len, *out_count}
+ * is then a valid offsets + lengths table over the same bytes, monotone
+ * whenever the input was packed, fixed-stride or monotone. The output arrays
+ * have capacity `count` (out_off 8-B, out_index / out_len 4-B aligned); count
+ * must not exceed 2^32 - 1. workspace: caller-owned device memory (4-B
+ * aligned) of at least nexg_match_select_workspace(count) bytes, one u32 per
+ * 256-frame tile. Positions come from ballots, ranks and scans only (no
+ * atomics): a run repeats bit for bit. count == 0 writes *out_count = 0 and
+ * launches nothing else. The scatter bounds every store by `count`, whatever
+ * the workspace holds. NEXG_EINVAL: an invalid frame table, a NULL pointer, a
+ * misaligned pointer, a short workspace. Three kernels on `stream`. */
+int nexg_match_select(nexg_ctx* ctx, const nexg_frames* frames, const nexg_match* matches,
+                      uint32_t any_mask, uint32_t all_mask, uint32_t none_mask, uint32_t* out_index,
+                      uint64_t* out_off, uint32_t* out_len, uint64_t* out_count, void* workspace,
+                      uint64_t workspace_bytes, void* stream);
+static inline uint64_t nexg_match_select_workspace(uint64_t count) {
+    const uint64_t tiles = (count + 255u) / 256u;
+    return 4u * ((tiles + 255u) / 256u * 256u) + 16u;
+}
+
 /* ---- flow keys, RSS hash and flow-affine partition (extension) -----------------
  * The reference has no flow notion; like the selection above this is an
  * extension, and the text below is its whole specification

@@ -27,6 +27,10 @@
  *                           no reference counterpart (an extension): frames
  *                           picked by rules over the parsed fields, and the
  *                           gather of their bytes and rows (include/nexg.h)
+ *   PatternSet, Engine::match / match_select / match_bufs
+ *                           no reference counterpart (an extension): up to 32
+ *                           byte strings looked for in every frame's payload,
+ *                           and the frames picked by what was found
  *   FlowOption, Engine::flow / flow_partition / flow_bufs
  *                           no reference counterpart (an extension): the
  *                           Toeplitz RSS hash of every frame's flow key and the
@@ -1033,6 +1037,49 @@ class Filter {
     }
 };
 
+/* ---- fixed-string match on frame bytes (extension: the reference has no payload search) --- */
+
+// Builder of a nexg_patterns (include/nexg.h): add / prefix / nocase append a
+// pattern of 1..16 bytes; frame() searches the whole frame instead of
+// Frame.payload. add throws nexg::Error for what cannot be stored, get()
+// where nexg_match_batch would return NEXG_EINVAL.
+//   PatternSet().prefix("\x16\x03", 2)                     payload starts with a TLS record
+//               .nocase("Host: ", 6)                         "host: " anywhere, in any case
+//               .add("\r\n\r\n", 4, 0, 16, 512)              starting at payload bytes 16..512
+class PatternSet {
+   public:
+    nexg_patterns s{};
+
+    PatternSet& add(const void* bytes, size_t len, uint8_t flags = 0, uint16_t off_lo = 0, uint16_t off_hi = 65535) {
+        if (s.n_patterns >= NEXG_MATCH_MAX_PATTERNS) throw Error("PatternSet: more than 32 patterns");
+        if (len == 0 || len > NEXG_MATCH_MAX_LEN) throw Error("PatternSet: a pattern is 1..16 bytes");
+        nexg_pattern& p = s.pat[s.n_patterns++];
+        memcpy(p.bytes, bytes, len);
+        p.len = (uint8_t)len;
+        p.flags = flags;
+        p.off_lo = off_lo;
+        p.off_hi = off_hi;
+        return *this;
+    }
+    PatternSet& add(const std::string& bytes, uint8_t flags = 0, uint16_t off_lo = 0, uint16_t off_hi = 65535) {
+        return add(bytes.data(), bytes.size(), flags, off_lo, off_hi);
+    }
+    PatternSet& prefix(const void* bytes, size_t len, uint8_t flags = 0) { return add(bytes, len, flags, 0, 0); }
+    PatternSet& nocase(const void* bytes, size_t len, uint16_t off_lo = 0, uint16_t off_hi = 65535) {
+        return add(bytes, len, NEXG_PAT_NOCASE, off_lo, off_hi);
+    }
+    PatternSet& frame(bool on = true) {
+        s.flags = on ? NEXG_MATCH_FRAME : 0u;
+        return *this;
+    }
+
+    // the set, checked as nexg_match_batch checks it
+    const nexg_patterns& get() const {
+        if (nexg_patterns_check(&s) != NEXG_OK) throw Error("PatternSet: not a valid nexg_patterns (include/nexg.h)");
+        return s;
+    }
+};
+
 /* ---- the engine --------------------------------------------------------- */
 
 // The calling thread's current device switched for a scope and restored after
@@ -1314,6 +1361,75 @@ class Engine {  // one nexg context on one gfx950 device, one stream
             check_hip(hipMemcpyAsync(out.lengths.data(), d_gl, k * 4, hipMemcpyDeviceToHost, stream_), "D2H");
         }
         if (total) check_hip(hipMemcpyAsync(out.data.data(), d_data, total, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        return out;
+    }
+
+    // A row per frame of a device-resident batch (an extension, include/nexg.h
+    // nexg_match_batch): which patterns of `set` occur in the frame's payload
+    // (records: the batch's NEXG_OUT_RECORD parse) or, with PatternSet::frame,
+    // anywhere in the frame (records may be null), and where the first one
+    // starts. `out` is a device array of frames.count rows (8-B aligned).
+    void match(const nexg_frames& frames, const nexg_record* records, const PatternSet& set, nexg_match* out) {
+        DeviceScope ds(device_);
+        check(nexg_match_batch(ctx_, &frames, records, &set.get(), out, stream_), "nexg_match_batch");
+    }
+
+    // Order-preserving selection by match's rows (nexg_match_select): frame i
+    // is kept when some bit of any_mask is in its mask (0: no such condition),
+    // every bit of all_mask is, and no bit of none_mask is. Device arrays of
+    // capacity frames.count; returns the number selected (one stream
+    // synchronisation). {frames.data, frames.data_bytes, out_off, out_len,
+    // returned count} is the selected batch, as after select.
+    uint64_t match_select(const nexg_frames& frames, const nexg_match* matches, uint32_t any_mask, uint32_t all_mask,
+                          uint32_t none_mask, uint32_t* out_index, uint64_t* out_off, uint32_t* out_len) {
+        DeviceScope ds(device_);
+        const uint64_t wsb = nexg_match_select_workspace(frames.count);
+        void* ws = scratch(44, wsb);
+        uint64_t* d_count = static_cast<uint64_t*>(scratch(45, 8));
+        check(nexg_match_select(ctx_, &frames, matches, any_mask, all_mask, none_mask, out_index, out_off, out_len, d_count,
+                                ws, wsb, stream_),
+              "nexg_match_select");
+        uint64_t k = 0;
+        check_hip(hipMemcpyAsync(&k, d_count, 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        return k;
+    }
+
+    // parse (NEXG_OUT_RECORD) + match + match_select of host frames: every
+    // frame's row, and the numbers of the frames the masks select
+    struct Matched {
+        std::vector<nexg_match> rows;
+        std::vector<uint32_t> index;
+        std::vector<uint64_t> offsets;  // of the selected frames in the packed upload (4-B aligned starts)
+        std::vector<uint32_t> lengths;
+    };
+    Matched match_bufs(const std::vector<std::vector<uint8_t>>& frames, const PatternSet& set, uint32_t any_mask = 0,
+                       uint32_t all_mask = 0, uint32_t none_mask = 0, ParseOption option = {},
+                       ParseMode mode = ParseMode::Lenient) {
+        DeviceScope ds(device_);
+        const uint64_t n = frames.size();
+        Matched out;
+        if (n == 0) return out;
+        HostBatch hb(*this, frames);
+        nexg_record* d_recs = static_cast<nexg_record*>(scratch(3, n * 64));
+        nexg_match* d_rows = static_cast<nexg_match*>(scratch(46, n * 8));
+        uint32_t* d_idx = static_cast<uint32_t*>(scratch(24, n * 4));
+        uint64_t* d_off = static_cast<uint64_t*>(scratch(25, n * 8));
+        uint32_t* d_len = static_cast<uint32_t*>(scratch(26, n * 4));
+        parse(hb.fb, option, mode, NEXG_OUT_RECORD, d_recs);
+        match(hb.fb, d_recs, set, d_rows);
+        const uint64_t k = match_select(hb.fb, d_rows, any_mask, all_mask, none_mask, d_idx, d_off, d_len);
+        out.rows.resize(n);
+        out.index.resize(k);
+        out.offsets.resize(k);
+        out.lengths.resize(k);
+        check_hip(hipMemcpyAsync(out.rows.data(), d_rows, n * 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        if (k) {
+            check_hip(hipMemcpyAsync(out.index.data(), d_idx, k * 4, hipMemcpyDeviceToHost, stream_), "D2H");
+            check_hip(hipMemcpyAsync(out.offsets.data(), d_off, k * 8, hipMemcpyDeviceToHost, stream_), "D2H");
+            check_hip(hipMemcpyAsync(out.lengths.data(), d_len, k * 4, hipMemcpyDeviceToHost, stream_), "D2H");
+        }
         check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
         return out;
     }

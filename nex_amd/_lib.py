@@ -59,6 +59,9 @@ def load():
         "nexg_gather_plan": (I, [P, ctypes.POINTER(abi.Frames), U32, P, P, P, U64, P]),
         "nexg_gather_frames": (I, [P, ctypes.POINTER(abi.Frames), P, P, U64, P]),
         "nexg_gather_rows": (I, [P, P, U32, U64, P, U64, P, P]),
+        "nexg_patterns_check": (I, [ctypes.POINTER(abi.PatternsC)]),
+        "nexg_match_batch": (I, [P, ctypes.POINTER(abi.Frames), P, ctypes.POINTER(abi.PatternsC), P, P]),
+        "nexg_match_select": (I, [P, ctypes.POINTER(abi.Frames), P, U32, U32, U32, P, P, P, P, P, U64, P]),
         "nexg_flow_batch": (I, [P, ctypes.POINTER(abi.Frames), P, ctypes.POINTER(abi.FlowOptionC), P, P]),
         "nexg_flow_partition": (I, [P, ctypes.POINTER(abi.Frames), P, U32, P, P, P, P, P, U64, P]),
         "nexg_flow_sort": (I, [P, P, U64, P, P, U64, P]),

@@ -481,6 +481,36 @@ def gather_plan_workspace(count):
     return 8 * ((tiles + 255) // 256 * 256) + 16
 
 
+# fixed-string match on frame bytes (nexg_match_batch / nexg_match_select; an
+# extension: the reference has no payload search)
+MATCH_MAX_PATTERNS = 32
+MATCH_MAX_LEN = 16
+PAT_NOCASE = 0x1
+MATCH_FRAME = 0x1
+PAT_NONE = 0xFF  # first_pat of a row whose mask is 0
+MATCH_DTYPE = np.dtype([("mask", "<u4"), ("first_off", "<u2"), ("first_pat", "u1"), ("reserved", "u1")])
+assert MATCH_DTYPE.itemsize == 8
+
+
+class PatternC(ctypes.Structure):
+    """struct nexg_pattern"""
+    _fields_ = [("bytes", ctypes.c_uint8 * 16), ("len", ctypes.c_uint8), ("flags", ctypes.c_uint8),
+                ("off_lo", ctypes.c_uint16), ("off_hi", ctypes.c_uint16), ("reserved", ctypes.c_uint8 * 10)]
+
+
+class PatternsC(ctypes.Structure):
+    """struct nexg_patterns"""
+    _fields_ = [("n_patterns", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("pat", PatternC * MATCH_MAX_PATTERNS)]
+
+
+assert ctypes.sizeof(PatternC) == 32 and ctypes.sizeof(PatternsC) == 1032
+
+
+def match_select_workspace(count):
+    """nexg_match_select_workspace: bytes of nexg_match_select's workspace."""
+    return select_workspace(count)
+
+
 # flow keys, RSS hash and flow-affine partition (nexg_flow_batch /
 # nexg_flow_partition; an extension: the reference has no flow notion)
 FLOW_SYMMETRIC, FLOW_NO_PORTS, FLOW_KEY = 0x1, 0x2, 0x4
@@ -544,7 +574,7 @@ def flow_table_workspace(n_in, n_groups):
 #: static inline helpers of include/nexg.h (header-only, not exported)
 HEADER_INLINE = ("nexg_sparse_decode", "nexg_grouped_code", "nexg_grouped_exc_slot", "nexg_offsets32_bases",
                  "nexg_offsets32_bytes", "nexg_decap_select_workspace", "nexg_dns_tile_first_bytes",
-                 "nexg_select_workspace", "nexg_gather_plan_workspace", "nexg_flow_partition_workspace",
+                 "nexg_select_workspace", "nexg_match_select_workspace", "nexg_gather_plan_workspace", "nexg_flow_partition_workspace",
                  "nexg_flow_sort_workspace", "nexg_flow_groups_workspace", "nexg_flow_table_workspace")
 
 #: every symbol include/nexg.h declares (tests check the .so exports them)
@@ -553,6 +583,7 @@ EXPORTED_SYMBOLS = (
     "nexg_ctx_last_error", "nexg_ctx_cu_count", "nexg_parse_batch", "nexg_checksum_batch", "nexg_decode_options", "nexg_probe_stream",
     "nexg_decap_batch", "nexg_decap_select", "nexg_dns_batch", "nexg_dns_entries",
     "nexg_filter_check", "nexg_select_batch", "nexg_gather_plan", "nexg_gather_frames", "nexg_gather_rows",
+    "nexg_patterns_check", "nexg_match_batch", "nexg_match_select",
     "nexg_flow_batch", "nexg_flow_partition", "nexg_flow_sort", "nexg_flow_groups",
     "nexg_flow_table_merge",
     "nexg_probe_span_clock", "nexg_probe_latency",

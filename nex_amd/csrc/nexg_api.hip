@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "match_core.hpp"
 #include "nexg_internal.hpp"
 
 struct nexg_ctx {
@@ -388,6 +389,49 @@ int nexg_select_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_recor
     DeviceGuard g(ctx);
     return launched(ctx, nexg::launch_select(a, records, f, out_index, out_off, out_len, out_rule, out_count,
                                              static_cast<uint32_t*>(workspace), as_stream(stream)));
+}
+
+int nexg_patterns_check(const nexg_patterns* set) {
+    return nexg::prepare_patterns(set, nullptr) ? NEXG_EINVAL : NEXG_OK;
+}
+
+int nexg_match_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records, const nexg_patterns* set,
+                     nexg_match* out, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    nexg::MatchSet s;
+    if (const char* why = nexg::prepare_patterns(set, &s)) return fail(ctx, NEXG_EINVAL, "match: %s", why);
+    const uint64_t count = frames->count;
+    if (int rc = check_count(ctx, "match", count)) return rc;
+    if (count && !records && !(s.flags & NEXG_MATCH_FRAME))
+        return fail(ctx, NEXG_EINVAL, "match: NULL records without NEXG_MATCH_FRAME%s", nullptr);
+    if (count && !out) return fail(ctx, NEXG_EINVAL, "NULL output%s", nullptr);
+    const bool reads_records = !(s.flags & NEXG_MATCH_FRAME);  // the whole-frame region never looks at them
+    if ((reads_records && misaligned(15u, records)) || misaligned(7u, out))
+        return fail(ctx, NEXG_EINVAL, "misaligned records or output%s", nullptr);
+    if (count == 0) return NEXG_OK;
+    const nexg::ParseArgs a = to_args(frames);
+    DeviceGuard g(ctx);
+    return launched(ctx, nexg::launch_match(a, records, s, out, as_stream(stream)));
+}
+
+int nexg_match_select(nexg_ctx* ctx, const nexg_frames* frames, const nexg_match* matches, uint32_t any_mask,
+                      uint32_t all_mask, uint32_t none_mask, uint32_t* out_index, uint64_t* out_off, uint32_t* out_len,
+                      uint64_t* out_count, void* workspace, uint64_t workspace_bytes, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    const uint64_t count = frames->count;
+    if (int rc = check_count(ctx, "match_select", count)) return rc;
+    if (!out_count) return fail(ctx, NEXG_EINVAL, "NULL out_count%s", nullptr);
+    if (count && (!matches || !out_index || !out_off || !out_len || !workspace))
+        return fail(ctx, NEXG_EINVAL, "NULL rows, output or workspace%s", nullptr);
+    if (int rc = check_workspace(ctx, "match_select", count, workspace_bytes, nexg_match_select_workspace(count))) return rc;
+    if (misaligned(7u, matches, out_off, out_count) || misaligned(3u, out_index, out_len, workspace))
+        return fail(ctx, NEXG_EINVAL, "misaligned rows, output or workspace%s", nullptr);
+    const nexg::ParseArgs a = to_args(frames);
+    DeviceGuard g(ctx);
+    return launched(ctx, nexg::launch_match_select(a, matches, any_mask, all_mask, none_mask, out_index, out_off, out_len,
+                                                   out_count, workspace, as_stream(stream)));
 }
 
 int nexg_gather_plan(nexg_ctx* ctx, const nexg_frames* sel, uint32_t align, uint64_t* out_offsets,

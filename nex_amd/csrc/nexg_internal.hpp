@@ -144,6 +144,16 @@ hipError_t launch_gather_frames(const ParseArgs& a, const uint64_t* out_offsets,
 hipError_t launch_gather_rows(const void* rows, uint32_t row_bytes, uint64_t rows_count, const uint32_t* index,
                               uint64_t n, void* out, hipStream_t s);
 
+// nexg_match_batch / nexg_match_select (nexg_match.hip). The set travels as a
+// kernel argument in the form match_core.hpp gives it. workspace: as
+// nexg_match_select_workspace sizes it (workspace_layout.hpp MatchSelectLayout),
+// left holding the tiles' exclusive scan.
+struct MatchSet;
+hipError_t launch_match(const ParseArgs& a, const nexg_record* recs, const MatchSet& s, nexg_match* out, hipStream_t st);
+hipError_t launch_match_select(const ParseArgs& a, const nexg_match* rows, uint32_t any_mask, uint32_t all_mask,
+                               uint32_t none_mask, uint32_t* out_index, uint64_t* out_off, uint32_t* out_len,
+                               uint64_t* out_count, void* workspace, hipStream_t s);
+
 // nexg_flow_batch / nexg_flow_partition (nexg_flow.hip). The Toeplitz key
 // travels as a kernel argument: its 40 bytes as ten big-endian word values.
 // workspace: as nexg_flow_partition_workspace lays it out.

@@ -20,6 +20,21 @@ inline T* region(void* workspace, uint64_t offset) {
     return reinterpret_cast<T*>(static_cast<char*>(workspace) + offset);
 }
 
+// nexg_match_select_workspace (the nexg_select_workspace formula): one u32 per
+// 256-frame tile, rounded up to whole scan steps of 256 tiles, and 16 spare bytes
+struct MatchSelectLayout {
+    uint64_t tiles;
+    uint64_t tile_count;  // u32[tiles]
+    uint64_t bytes;
+    static MatchSelectLayout from(uint64_t count) {
+        MatchSelectLayout w;
+        w.tiles = (count + 255u) / 256u;
+        w.tile_count = 0;
+        w.bytes = 4u * ((w.tiles + 255u) / 256u * 256u) + 16u;
+        return w;
+    }
+};
+
 // nexg_flow_partition_workspace: the scan's total, one u32 per chunk of 1024
 // counters (an even number of slots, so the counters start on 8 B), then the
 // buckets x tiles counters, bucket-major

@@ -393,6 +393,65 @@ class Engine:
                          hints=abi.FRAMES_MONOTONE if _ordered(batch) else 0)
         return (idx[:k], sel, rule[:k]) if want_rule else (idx[:k], sel)
 
+    def match(self, batch: FrameBatch, records, pset, stream=None):
+        """Fixed-string match on frame bytes (nexg_match_batch; an extension,
+        the reference has no payload search): which of up to 32 patterns of
+        1..16 bytes occur in each frame's payload (or, with
+        PatternSet(frame=True), anywhere in the frame), and where the first
+        one starts. `records` is the uint8 device tensor a NEXG_OUT_RECORD
+        parse of `batch` returned (None is valid with frame=True), `pset` a
+        nex_amd.match.PatternSet. Returns a uint8 device tensor holding
+        nexg_match[count] (abi.MATCH_DTYPE). One kernel, no synchronisation.
+
+        The recipe: parse, match, narrow the table to the frames that carry
+        what is looked for, compact the records, run the follow-up passes on
+        those frames only, copy out just what matched:
+
+            rec = eng.parse(batch, out_kind=abi.OUT_RECORD)
+            rows = eng.match(batch, rec, PatternSet([Pattern(b"Host: ", nocase=True), Pattern.prefix(b"\\x16\\x03")]))
+            idx, sel = eng.match_select(batch, rows, any=0b11)
+            rec_sel = eng.gather_rows(rec, 64, idx)          # records of the selected frames
+            dns, tile_first, entries, total = eng.dns(sel, rec_sel)
+            dense = eng.gather(sel)                          # a packed batch of the selected bytes
+
+        It composes with Engine.select through the tables: match the table
+        select returned (with the gathered records), or select on the table
+        match_select returned."""
+        torch = _torch()
+        pc = pset.to_c()  # ValueError for what nexg_match_batch rejects
+        out = torch.empty(max(batch.count, 1) * 8, dtype=torch.uint8, device=self.torch_device)
+        self._check(self.lib.nexg_match_batch(self.ctx, _frames(batch), _ptr(records), ctypes.byref(pc), _ptr(out),
+                                              self._stream(stream)))
+        return out[: batch.count * 8]
+
+    def match_select(self, batch: FrameBatch, matches, any: int = 0, all: int = 0, none: int = 0,  # noqa: A002
+                     stream=None):
+        """Order-preserving selection by Engine.match's rows
+        (nexg_match_select): frame i is selected when some bit of `any` is in
+        its mask (any = 0: no such condition), every bit of `all` is, and no
+        bit of `none` is; all three zero select every frame. Returns (index,
+        selected) exactly as Engine.select returns them: index an int32
+        device tensor (bit patterns of u32) with the frame number of each
+        selected frame, selected a FrameBatch (offsets + lengths) over the
+        same data whose count is the selected count. Allocates the workspace
+        and reads the selected count back: one synchronisation of the stream."""
+        torch = _torch()
+        for name, v in (("any", any), ("all", all), ("none", none)):
+            if not 0 <= int(v) <= 0xFFFFFFFF:
+                raise ValueError(f"{name} is a 32-bit mask")
+        count = batch.count
+        idx, off, ln = self._table(count)
+        cnt = torch.zeros(1, dtype=torch.int64, device=self.torch_device)
+        ws_bytes = abi.match_select_workspace(count)
+        ws = self._workspace(ws_bytes)
+        self._check(self.lib.nexg_match_select(self.ctx, _frames(batch), _ptr(matches), int(any), int(all), int(none),
+                                               _ptr(idx), _ptr(off), _ptr(ln), _ptr(cnt), _ptr(ws), ws_bytes,
+                                               self._stream(stream)))
+        k = int(cnt.item())  # waits for the kernels
+        sel = FrameBatch(data=batch.data, count=k, offsets=off[:k], lengths=ln[:k],
+                         hints=abi.FRAMES_MONOTONE if _ordered(batch) else 0)
+        return idx[:k], sel
+
     def gather(self, sel: FrameBatch, align: int = 1, stream=None):
         """Copy the frames of `sel` (usually Engine.select's table) into one
         dense buffer (nexg_gather_plan + nexg_gather_frames). Returns a new
