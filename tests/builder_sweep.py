@@ -1,5 +1,5 @@
-"""Differential sweep of the frame builders (nex_amd/csrc/nexg_build.hip): the
-case grid, the launcher predicates restated as DISPATCH_CLASSES, the inputs
+"""Differential sweep of the frame builders (nex_amd/csrc/nexg_build.hip and
+nexg_build_probe.hip): the case grid, the launcher predicates restated as DISPATCH_CLASSES, the inputs
 with planted extreme and solved-checksum rows, the oracle's expected bytes and
 the whole-buffer comparer. tests/test_builder_sweep.py checks the grid, the
 corpus and the comparer on the CPU; tests/test_gpu_builder_sweep.py runs it.
@@ -14,7 +14,7 @@ A Case names its optional per-frame arrays by the row they fill:
   multicast   ndp_ns: eth_dst_multicast (not an array)
 
 udp4_tuples always carries src, p0, p1 and ip_id in its records. Whatever
-nexg_build.hip's launchers test is restated here, so DISPATCH_CLASSES must be
+the launchers of those two files test is restated here, so DISPATCH_CLASSES must be
 updated whenever a launcher's predicates change."""
 import ctypes
 import itertools

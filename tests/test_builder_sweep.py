@@ -1,5 +1,5 @@
 """CPU: the builder sweep's grid, corpus and comparer (tests/builder_sweep.py),
-checked without a GPU: every dispatch class of nexg_build.hip's launchers is
+checked without a GPU: every dispatch class of the builders' launchers is
 reached at every count, the oracle's frames carry the checksum edges and agree
 with an independent Internet checksum, and the comparer reports every seeded
 defect."""

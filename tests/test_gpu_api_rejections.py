@@ -380,3 +380,49 @@ def test_empty_batch(calls, entry):
     torch.cuda.synchronize()
     if zeroed:
         assert (out.cpu().numpy() == 0).all(), (entry, zeroed)
+
+
+# ---- the builders: a batch whose tiles do not fit one grid -------------------
+# One workgroup builds a tile of 256 frames and a grid holds 2^32 - 1
+# workgroups, so 2^40 + 1 frames cannot be launched: every build entry answers
+# NEXG_ELAUNCH ("HIP: invalid argument") and launches nothing. The buffers hold
+# 256 frames, so a kernel that ran a truncated grid of one tile would write them
+# and nothing else.
+BUILD_FRAMES = 256
+BUILD_ENTRIES = {  # entry: frame bytes
+    "nexg_build_udp4_batch": 42, "nexg_build_udp4_tuples": 42, "nexg_build_udp6_batch": 62, "nexg_build_tcp_batch": 54,
+    "nexg_build_icmp_echo_batch": 42, "nexg_build_arp_batch": 42, "nexg_build_ndp_ns_batch": 86,
+}
+
+
+@pytest.mark.parametrize("entry", list(BUILD_ENTRIES))
+def test_build_count_beyond_one_grid(engine, entry):
+    import torch
+    flen = BUILD_ENTRIES[entry]
+    a4, a6, b4, b6, tuples = (torch.zeros(BUILD_FRAMES * w, dtype=torch.uint8, device="cuda") for w in (4, 16, 4, 16, 16))
+    out = torch.full((BUILD_FRAMES * flen,), 0xA5, dtype=torch.uint8, device="cuda")
+    extra = ()
+    if entry in ("nexg_build_udp4_batch", "nexg_build_udp4_tuples"):
+        p = abi.Udp4Build()
+        if entry == "nexg_build_udp4_batch":
+            p.dst_ip = a4.data_ptr()
+        else:
+            extra = (ctypes.c_void_p(tuples.data_ptr()),)
+    elif entry == "nexg_build_udp6_batch":
+        p = abi.Udp6Build()
+        p.src_ip, p.dst_ip = a6.data_ptr(), b6.data_ptr()
+    elif entry == "nexg_build_arp_batch":
+        p = abi.ArpBuild()
+        p.target_ip, p.hw_addr_len, p.proto_addr_len = a4.data_ptr(), 6, 4
+    else:
+        p = {"nexg_build_tcp_batch": abi.TcpBuild, "nexg_build_icmp_echo_batch": abi.IcmpEchoBuild,
+             "nexg_build_ndp_ns_batch": abi.NdpNsBuild}[entry]()
+        six = entry == "nexg_build_ndp_ns_batch"
+        p.ip.family = 6 if six else 4
+        p.ip.src_ip, p.ip.dst_ip = (a6.data_ptr(), b6.data_ptr()) if six else (a4.data_ptr(), b4.data_ptr())
+    p.count = (1 << 40) + 1
+    rc = getattr(engine.lib, entry)(engine.ctx, ctypes.byref(p), *extra, ctypes.c_void_p(out.data_ptr()), flen, None)
+    text = engine.lib.nexg_ctx_last_error(engine.ctx).decode()
+    torch.cuda.synchronize()
+    assert (rc, text) == (abi.ELAUNCH, "HIP: invalid argument"), (entry, rc, text)
+    assert bool((out == 0xA5).all()), entry

@@ -1,5 +1,5 @@
 """GPU: differential sweep of the seven frame builders over the grid of
-tests/builder_sweep.py: every dispatch class of nexg_build.hip's launchers at
+tests/builder_sweep.py: every dispatch class of the builders' launchers at
 counts 1, 255, 256, 257 and 513, aligned and unaligned `out`, the stride band
 edges, payload lengths around kSmallPay and up to the largest the entry
 accepts, payloads at every address shift, the TCP option sets and the optional

@@ -2,6 +2,7 @@
 """Kernel time of the udp_ping-family builders other than the IPv4 probe batch
 (SURVEY.md 8(f) row 3): udp_ping's IPv6 branch (62 B), tcp_ping SYN without
 and with its option list (54 / 66 B), icmp_ping echo (IPv4 42 B, IPv6 62 B),
+the arp.rs request (42 B) and the ndp.rs neighbor solicitation (86 B),
 16M frames each, per-frame addresses / ports / ids from random device arrays,
 HIP events around the launches. Prints one JSON object: per shape kernel ms
 and the fraction of 8 TB/s written. Run once per NEXG_BUILD_LDS_PAD setting
@@ -47,6 +48,9 @@ def main():
                                                         options=TCP_PING_OPTS, ip_id=ipid, out=out)),
         "icmp4_echo_42B": (42, lambda out: eng.build_icmp_echo(4, a4s, a4d, sp, dp, ip_id=ipid, out=out)),
         "icmp6_echo_62B": (62, lambda out: eng.build_icmp_echo(6, a6s, a6d, sp, dp, out=out)),
+        # the arp.rs / ndp.rs probes: a sender and a target per frame / a source and a target per frame
+        "arp_42B": (42, lambda out: eng.build_arp(a4d, sender_ip=a4s, out=out)),
+        "ndp_ns_86B": (86, lambda out: eng.build_ndp_ns(a6s, a6d, out=out)),
     }
     if args.probe:  # the probe batches of nex_amd/probes.py (one source, a destination per frame)
         from nex_amd import probes

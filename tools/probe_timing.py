@@ -3,7 +3,7 @@
 probe batch (16M frames, nex_amd/probes.py shapes and udp_ping's IPv4 probe
 batch) through a measurement build of the library (-DNEXG_PROBE_TIMING=1:
 thread 0 of every workgroup stamps s_memtime at its phase boundaries, see
-nexg_build.hip), then per shape: the kernel time, the shader clock
+build_core.hpp), then per shape: the kernel time, the shader clock
 (s_memtime ticks / 100-MHz ticks), each phase's mean cycles, and how many
 workgroups were alive on average (sum of workgroup lifetimes / kernel time).
 Phases: [0-1] prologue (destination load issued, template / pattern, first
