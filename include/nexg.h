@@ -976,6 +976,122 @@ static inline uint64_t nexg_match_select_workspace(uint64_t count) {
     return 4u * ((tiles + 255u) / 256u * 256u) + 16u;
 }
 
+/* ---- header rewrite (mutable setters, the other half of SURVEY.md a20) ----------
+ * nexg_rewrite_batch changes header fields of the frames in place, with the
+ * semantics of the reference's mutable setters under ChecksumMode::Automatic
+ * (checksum.rs:8-14, ipv4.rs:621-626: every set recomputes the checksum):
+ * MutableEthernetPacket::set_destination / set_source, MutableIpv4Packet::
+ * set_source / set_destination / set_ttl / set_dscp / set_ecn,
+ * MutableIpv6Packet::set_source / set_destination / set_hop_limit /
+ * set_traffic_class, MutableTcpPacket / MutableUdpPacket::set_source /
+ * set_destination (examples/mutable_chaining.rs is the example caller). An
+ * action names the fields and their values; a set holds up to 16 actions, and
+ * a per-frame index picks one: with the out_rule of nexg_select_batch as the
+ * index, rule j of a filter gets action j. The text below is the whole
+ * specification (nex_amd/rewrite.py rewrite_host restates it on the host).
+ *
+ * Per frame i, in this order:
+ * 1. Action. a = action_index ? action_index[i] : 0. If a >= n_actions
+ *    (NEXG_ACTION_NONE and any other value: the index is caller memory and
+ *    never indexes past the set) the frame is untouched and its row is
+ *    {0, 0, NEXG_ACTION_NONE, 0, 0}. A frame whose extent is invalid (the
+ *    fix-up's rule: it leaves [0, data_bytes) or is longer than 65535) is
+ *    untouched and gets {0, 0, a, 0, 0}.
+ * 2. Views: exactly those of the fix-up above. The Ethernet view: not
+ *    NEXG_PARSE_FROM_IP, len >= 14. The IPv4 view under MutableIpv4Packet::
+ *    new's conditions, the IPv6 view (>= 40 B, payload = everything after 40,
+ *    extension headers not walked), L = the IP header's offset (14, or
+ *    ip_offset with NEXG_PARSE_FROM_IP, where the version nibble picks the
+ *    family). The UDP / TCP / ICMP / ICMPv6 views over the IP view's payload
+ *    [P, P + m) under the fix-up's length conditions. In INCREMENTAL mode
+ *    only, an IPv4 frame whose 13-bit fragment offset is not 0 has no L4 view
+ *    (a later fragment holds no L4 header).
+ * 3. Fields: each is written when its bit is set and its view exists. MACs
+ *    need the Ethernet view. Addresses need the IP view of action.family
+ *    (IPv4: bytes L+12.. and L+16..; IPv6: L+8.. and L+24..). TTL: IPv4 byte
+ *    L+8, IPv6 byte L+7. TOS: IPv4 byte L+1; IPv6 traffic class = the low
+ *    nibble of byte L and the high nibble of byte L+1. Ports need the UDP or
+ *    TCP view: bytes P..P+1 and P+2..P+3, big-endian. `applied` gets the bit
+ *    of every field written, whether or not the value changed (the reference
+ *    marks a checksum dirty on every set).
+ * 4. Dirty checksums. IPv4 header: the IPv4 view exists and any of IP_SRC,
+ *    IP_DST, TTL, DEC_TTL, TOS was applied. L4: an L4 view exists and a port
+ *    was applied, or an address was applied and the protocol is not ICMPv4 (1:
+ *    no pseudo-header; ICMPv6 has one). IPv6 TTL and TOS dirty nothing.
+ * 5. Default mode (flags == 0, RECOMPUTE): the frame's final bytes are the
+ *    edited bytes passed through nexg_recompute_checksums_batch with `which` =
+ *    the dirty set. Like the reference's views it knows nothing of fragments.
+ * 6. NEXG_REWRITE_INCREMENTAL: RFC 1624 eqn. 3 on the stored value,
+ *    HC' = ~fold(~HC + sum(~m_k + m'_k)) over the 16-bit words of every
+ *    applied field the checksum covers (IPv4 header: the words at L+0 (TOS),
+ *    L+8 (TTL) and the address words; L4: the pseudo-header address words and
+ *    the port words); fold is the end-around carry fold to 16 bits. A UDP view
+ *    over IPv4 whose stored checksum is 0 ("none") keeps 0 and `fixed` does
+ *    not get NEXG_FIX_L4. There is no 0 -> 0xFFFF mapping (the reference has
+ *    none). A frame whose stored checksums were the fix-up's
+ *    values comes out byte-identical to RECOMPUTE; a wrong checksum stays
+ *    wrong by the same amount. Only header bytes are used: at most the
+ *    Ethernet, IP and first 20 L4 bytes. The kernel loads them as the frame's
+ *    first 16-B blocks (at most six) and never sums the payload.
+ *
+ * Stores touch only the bytes of the fields and checksum fields named above,
+ * as single bytes; every other byte of frames->data keeps its value, the gaps
+ * between frames included. Frames must not overlap (then the result is
+ * unspecified, but no store leaves a frame's own extent). No atomics: a run
+ * repeats bit for bit. Reads follow the 16-B block rule of the frame batch
+ * layout. count == 0 launches nothing; one kernel on `stream`; no workspace.
+ *
+ * NEXG_EINVAL for a set (nexg_actions_check tells): n_actions 0 or above 16,
+ * unknown flags or sets bits, nonzero reserved, SET_TTL together with
+ * DEC_TTL, DEC_TTL with ttl == 0, an address set with a family other than 4
+ * or 6, a nonzero family without an address set, SET_TOS with tos_mask == 0
+ * or tos & ~tos_mask. sets == 0 is valid: the "leave it" action of a rule.
+ * From nexg_rewrite_batch itself: a NULL frames, option or actions, an
+ * invalid frame table, a misaligned out. */
+#define NEXG_SET_ETH_DST  0x001u  /* frame bytes 0..5  = eth_dst */
+#define NEXG_SET_ETH_SRC  0x002u  /* frame bytes 6..11 = eth_src */
+#define NEXG_SET_IP_SRC   0x004u
+#define NEXG_SET_IP_DST   0x008u
+#define NEXG_SET_SRC_PORT 0x010u
+#define NEXG_SET_DST_PORT 0x020u
+#define NEXG_SET_TTL      0x040u  /* IPv4 ttl / IPv6 hop limit = ttl */
+#define NEXG_DEC_TTL      0x080u  /* ... = old > ttl ? old - ttl : 0 */
+#define NEXG_SET_TOS      0x100u  /* IPv4 byte 1 / IPv6 traffic class = (old & ~tos_mask) | tos */
+#define NEXG_SET_ALL      0x1FFu
+#define NEXG_REWRITE_INCREMENTAL 0x1u   /* nexg_actions.flags */
+#define NEXG_REWRITE_MAX_ACTIONS 16
+#define NEXG_ACTION_NONE 0xFFu
+typedef struct nexg_action {      /* 64 bytes */
+    uint32_t sets;                /* NEXG_SET_* / NEXG_DEC_TTL */
+    uint8_t family;               /* 4 or 6 with an address set, else 0 */
+    uint8_t ttl, tos, tos_mask;
+    uint16_t src_port, dst_port;  /* host order values */
+    uint8_t eth_dst[6], eth_src[6];
+    uint8_t src[16], dst[16];     /* network order; family 4 uses the first 4 bytes */
+    uint8_t reserved[8];          /* must be 0 */
+} nexg_action;
+typedef struct nexg_actions {     /* host memory, 1032 bytes; read during the call only */
+    uint32_t n_actions, flags;
+    nexg_action actions[NEXG_REWRITE_MAX_ACTIONS];
+} nexg_actions;
+typedef struct nexg_rewritten {   /* 8 bytes */
+    uint16_t applied;             /* NEXG_SET_* / NEXG_DEC_TTL bits of the fields written */
+    uint8_t fixed;                /* NEXG_FIX_IP / NEXG_FIX_L4: checksum fields written */
+    uint8_t action;               /* the action used, NEXG_ACTION_NONE if none */
+    uint16_t ip_csum, l4_csum;    /* values written (0 where not written) */
+} nexg_rewritten;
+
+/* NEXG_OK when nexg_rewrite_batch would accept the set, else NEXG_EINVAL.
+ * Host only: no context, no device. */
+int nexg_actions_check(const nexg_actions* actions);
+
+/* action_index: device memory, `count` entries, or NULL (action 0 for every
+ * frame). out (optional, 8-B aligned): nexg_rewritten[count]. The batch's
+ * data must be writable device memory. */
+int nexg_rewrite_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_parse_option* option,
+                       const nexg_actions* actions, const uint8_t* action_index, nexg_rewritten* out,
+                       void* stream);
+
 /* ---- flow keys, RSS hash and flow-affine partition (extension) -----------------
  * The reference has no flow notion; like the selection above this is an
  * extension, and the text below is its whole specification

@@ -31,6 +31,12 @@
  *                           no reference counterpart (an extension): up to 32
  *                           byte strings looked for in every frame's payload,
  *                           and the frames picked by what was found
+ *   Action, ActionSet, Engine::rewrite / rewrite_bufs
+ *                           the mutable views' setters under
+ *                           ChecksumMode::Automatic (MutableEthernetPacket,
+ *                           MutableIpv4Packet, MutableIpv6Packet, MutableTcpPacket,
+ *                           MutableUdpPacket; examples/mutable_chaining.rs) on
+ *                           a batch in place, one action per filter rule
  *   FlowOption, Engine::flow / flow_partition / flow_bufs
  *                           no reference counterpart (an extension): the
  *                           Toeplitz RSS hash of every frame's flow key and the
@@ -1080,6 +1086,92 @@ class PatternSet {
     }
 };
 
+/* ---- header rewrite (the mutable setters under ChecksumMode::Automatic) ---------- */
+
+// Builder of one nexg_action (include/nexg.h): each call names a field and its
+// value, as the reference's setters do one by one.
+//   Action().nat4(src, dst).ports(40000, 443).dec_ttl(1)   NAT44 with ports, one hop
+//   Action().mac(next_hop, mine).dec_ttl(1)                the router
+//   Action()                                                leave it
+class Action {
+   public:
+    nexg_action a{};
+
+    Action& eth_dst(const uint8_t mac[6]) { return bytes(NEXG_SET_ETH_DST, a.eth_dst, mac, 6); }
+    Action& eth_src(const uint8_t mac[6]) { return bytes(NEXG_SET_ETH_SRC, a.eth_src, mac, 6); }
+    Action& mac(const uint8_t dst[6], const uint8_t src[6]) { return eth_dst(dst).eth_src(src); }
+    // addresses in network order: 4 bytes (family 4) or 16 (family 6)
+    Action& ip_src(uint8_t family, const uint8_t* addr) { return address(NEXG_SET_IP_SRC, a.src, family, addr); }
+    Action& ip_dst(uint8_t family, const uint8_t* addr) { return address(NEXG_SET_IP_DST, a.dst, family, addr); }
+    Action& nat4(const uint8_t src[4], const uint8_t dst[4]) { return ip_src(4, src).ip_dst(4, dst); }
+    Action& nat6(const uint8_t src[16], const uint8_t dst[16]) { return ip_src(6, src).ip_dst(6, dst); }
+    Action& src_port(uint16_t p) {
+        a.sets |= NEXG_SET_SRC_PORT;
+        a.src_port = p;
+        return *this;
+    }
+    Action& dst_port(uint16_t p) {
+        a.sets |= NEXG_SET_DST_PORT;
+        a.dst_port = p;
+        return *this;
+    }
+    Action& ports(uint16_t src, uint16_t dst) { return src_port(src).dst_port(dst); }
+    Action& set_ttl(uint8_t ttl) {
+        a.sets |= NEXG_SET_TTL;
+        a.ttl = ttl;
+        return *this;
+    }
+    Action& dec_ttl(uint8_t by = 1) {
+        a.sets |= NEXG_DEC_TTL;
+        a.ttl = by;
+        return *this;
+    }
+    // (old & ~mask) | tos: mask 0xFC is set_dscp (tos = dscp << 2), mask 0x03 set_ecn
+    Action& set_tos(uint8_t tos, uint8_t mask = 0xFF) {
+        a.sets |= NEXG_SET_TOS;
+        a.tos = tos;
+        a.tos_mask = mask;
+        return *this;
+    }
+
+   private:
+    Action& bytes(uint32_t bit, uint8_t* to, const uint8_t* from, size_t n) {
+        a.sets |= bit;
+        memcpy(to, from, n);
+        return *this;
+    }
+    Action& address(uint32_t bit, uint8_t* to, uint8_t family, const uint8_t* addr) {
+        if (family != 4 && family != 6) throw Error("Action: an address family is 4 or 6");
+        if (a.family && a.family != family) throw Error("Action: addresses of two families");
+        a.family = family;
+        memset(to, 0, 16);
+        return bytes(bit, to, addr, family == 4 ? 4 : 16);
+    }
+};
+
+// Builder of a nexg_actions: up to 16 actions; incremental() updates the stored
+// checksums by RFC 1624 instead of recomputing them. add throws nexg::Error
+// for the 17th action, get() where nexg_rewrite_batch would return NEXG_EINVAL.
+class ActionSet {
+   public:
+    nexg_actions s{};
+
+    ActionSet& add(const Action& action) {
+        if (s.n_actions >= NEXG_REWRITE_MAX_ACTIONS) throw Error("ActionSet: more than 16 actions");
+        s.actions[s.n_actions++] = action.a;
+        return *this;
+    }
+    ActionSet& incremental(bool on = true) {
+        s.flags = on ? NEXG_REWRITE_INCREMENTAL : 0u;
+        return *this;
+    }
+    // the set, checked as nexg_rewrite_batch checks it
+    const nexg_actions& get() const {
+        if (nexg_actions_check(&s) != NEXG_OK) throw Error("ActionSet: not a valid nexg_actions (include/nexg.h)");
+        return s;
+    }
+};
+
 /* ---- the engine --------------------------------------------------------- */
 
 // The calling thread's current device switched for a scope and restored after
@@ -1949,6 +2041,45 @@ class Engine {  // one nexg context on one gfx950 device, one stream
         for (uint64_t i = 0; i < n; i++)
             std::copy(data.begin() + hb.offs[i], data.begin() + hb.offs[i] + hb.lens[i], frames[i].begin());
         return fx;
+    }
+
+    // Header fields of a device-resident batch rewritten in place
+    // (nexg_rewrite_batch; MutableEthernetPacket::set_destination / set_source,
+    // MutableIpv4Packet / MutableIpv6Packet::set_source / set_destination /
+    // set_ttl / set_hop_limit / set_dscp / set_ecn / set_traffic_class,
+    // MutableTcpPacket / MutableUdpPacket::set_source / set_destination under
+    // ChecksumMode::Automatic). action_index: a device array with one action
+    // number per frame (the out_rule of select: rule j gets action j;
+    // NEXG_ACTION_NONE leaves a frame alone) or null (action 0 for all); out:
+    // a device array of frames.count rows (8-B aligned) or null.
+    void rewrite(const nexg_frames& frames, const ActionSet& actions, const uint8_t* action_index = nullptr,
+                 nexg_rewritten* out = nullptr, ParseOption option = {}) {
+        DeviceScope ds(device_);
+        const nexg_parse_option o{option.flags(ParseMode::Lenient), (uint32_t)option.offset};
+        check(nexg_rewrite_batch(ctx_, &frames, &o, &actions.get(), action_index, out, stream_), "nexg_rewrite_batch");
+    }
+
+    // rewrite of host frames, in place; index: one action number per frame, or
+    // empty (action 0 for all). One nexg_rewritten per frame says what was written.
+    std::vector<nexg_rewritten> rewrite_bufs(std::vector<std::vector<uint8_t>>& frames, const ActionSet& actions,
+                                             const std::vector<uint8_t>& index = {}, ParseOption option = {}) {
+        DeviceScope ds(device_);
+        const uint64_t n = frames.size();
+        std::vector<nexg_rewritten> rows(n);
+        if (!index.empty() && index.size() != n) throw Error("rewrite_bufs: one action number per frame");
+        if (n == 0) return rows;
+        HostBatch hb(*this, frames);
+        nexg_rewritten* d_rows = static_cast<nexg_rewritten*>(scratch(3, n * sizeof(nexg_rewritten)));
+        const uint8_t* d_index = index.empty() ? nullptr : static_cast<const uint8_t*>(upload(47, index.data(), n));
+        rewrite(hb.fb, actions, d_index, d_rows, option);
+        std::vector<uint8_t> data(hb.data.size());
+        check_hip(hipMemcpyAsync(data.data(), const_cast<uint8_t*>(hb.fb.data), data.size(), hipMemcpyDeviceToHost,
+                                 stream_), "D2H");
+        check_hip(hipMemcpyAsync(rows.data(), d_rows, n * sizeof(nexg_rewritten), hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        for (uint64_t i = 0; i < n; i++)
+            std::copy(data.begin() + hb.offs[i], data.begin() + hb.offs[i] + hb.lens[i], frames[i].begin());
+        return rows;
     }
 
    private:

@@ -62,6 +62,9 @@ def load():
         "nexg_patterns_check": (I, [ctypes.POINTER(abi.PatternsC)]),
         "nexg_match_batch": (I, [P, ctypes.POINTER(abi.Frames), P, ctypes.POINTER(abi.PatternsC), P, P]),
         "nexg_match_select": (I, [P, ctypes.POINTER(abi.Frames), P, U32, U32, U32, P, P, P, P, P, U64, P]),
+        "nexg_actions_check": (I, [ctypes.POINTER(abi.ActionsC)]),
+        "nexg_rewrite_batch": (I, [P, ctypes.POINTER(abi.Frames), ctypes.POINTER(abi.ParseOptionC),
+                                   ctypes.POINTER(abi.ActionsC), P, P, P]),
         "nexg_flow_batch": (I, [P, ctypes.POINTER(abi.Frames), P, ctypes.POINTER(abi.FlowOptionC), P, P]),
         "nexg_flow_partition": (I, [P, ctypes.POINTER(abi.Frames), P, U32, P, P, P, P, P, U64, P]),
         "nexg_flow_sort": (I, [P, P, U64, P, P, U64, P]),

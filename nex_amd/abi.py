@@ -511,6 +511,34 @@ def match_select_workspace(count):
     return select_workspace(count)
 
 
+# header rewrite (nexg_rewrite_batch: the mutable setters under ChecksumMode::Automatic)
+SET_ETH_DST, SET_ETH_SRC, SET_IP_SRC, SET_IP_DST = 0x001, 0x002, 0x004, 0x008
+SET_SRC_PORT, SET_DST_PORT, SET_TTL, DEC_TTL, SET_TOS = 0x010, 0x020, 0x040, 0x080, 0x100
+SET_ALL = 0x1FF
+REWRITE_INCREMENTAL = 0x1
+REWRITE_MAX_ACTIONS = 16
+ACTION_NONE = 0xFF
+REWRITTEN_DTYPE = np.dtype([("applied", "<u2"), ("fixed", "u1"), ("action", "u1"), ("ip_csum", "<u2"),
+                            ("l4_csum", "<u2")])
+assert REWRITTEN_DTYPE.itemsize == 8
+
+
+class ActionC(ctypes.Structure):
+    """struct nexg_action"""
+    _fields_ = [("sets", ctypes.c_uint32), ("family", ctypes.c_uint8), ("ttl", ctypes.c_uint8),
+                ("tos", ctypes.c_uint8), ("tos_mask", ctypes.c_uint8), ("src_port", ctypes.c_uint16),
+                ("dst_port", ctypes.c_uint16), ("eth_dst", ctypes.c_uint8 * 6), ("eth_src", ctypes.c_uint8 * 6),
+                ("src", ctypes.c_uint8 * 16), ("dst", ctypes.c_uint8 * 16), ("reserved", ctypes.c_uint8 * 8)]
+
+
+class ActionsC(ctypes.Structure):
+    """struct nexg_actions"""
+    _fields_ = [("n_actions", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("actions", ActionC * REWRITE_MAX_ACTIONS)]
+
+
+assert ctypes.sizeof(ActionC) == 64 and ctypes.sizeof(ActionsC) == 1032
+
+
 # flow keys, RSS hash and flow-affine partition (nexg_flow_batch /
 # nexg_flow_partition; an extension: the reference has no flow notion)
 FLOW_SYMMETRIC, FLOW_NO_PORTS, FLOW_KEY = 0x1, 0x2, 0x4
@@ -584,6 +612,7 @@ EXPORTED_SYMBOLS = (
     "nexg_decap_batch", "nexg_decap_select", "nexg_dns_batch", "nexg_dns_entries",
     "nexg_filter_check", "nexg_select_batch", "nexg_gather_plan", "nexg_gather_frames", "nexg_gather_rows",
     "nexg_patterns_check", "nexg_match_batch", "nexg_match_select",
+    "nexg_actions_check", "nexg_rewrite_batch",
     "nexg_flow_batch", "nexg_flow_partition", "nexg_flow_sort", "nexg_flow_groups",
     "nexg_flow_table_merge",
     "nexg_probe_span_clock", "nexg_probe_latency",

@@ -25,6 +25,112 @@ NEXG_HD void put_be16(uint8_t* p, uint32_t v) {
     p[1] = (uint8_t)v;
 }
 
+// The mutable views' constructor conditions over one frame of `len` bytes read
+// through accessor o.f, stated
+// once for recompute_frame below and rewrite_frame (rewrite_core.hpp). The IP
+// part: the Ethernet view (ethernet.rs:355-361) or the raw IP packet at
+// ip_offset, then MutableIpv4Packet::new (ipv4.rs:540-566) or
+// MutableIpv6Packet::new (>= 40 B, payload = the rest; extension headers are
+// not walked).
+struct FrameViews {
+    uint32_t L = 14;     // offset of the IP header
+    uint32_t family = 0; // 4 / 6 when that IP view exists, else 0
+    uint32_t hl = 0;     // IP header bytes (IPv6: 40)
+    uint32_t P = 0, m = 0;  // the IP view's payload_mut: f[P, P + m)
+    uint32_t proto = 0;  // protocol / next header byte
+    bool eth = false;    // the Ethernet view exists
+    bool l4 = false;     // the protocol has an L4 view kind (17, 6, 1 over IPv4 / 58 over IPv6)
+};
+
+template <class O>
+NEXG_HD FrameViews frame_views(const O& o, uint32_t len, uint32_t opt_flags, uint32_t ip_offset) {
+    FrameViews v;
+    uint32_t family = 0;
+    if (opt_flags & NEXG_PARSE_FROM_IP) {
+        v.L = ip_offset;
+        const uint32_t ver = v.L < len ? o.f.u8(v.L) >> 4 : 0u;
+        family = ver == 4u ? 4u : (ver == 6u ? 6u : 0u);
+    } else if (len >= 14u) {
+        v.eth = true;
+        const uint32_t et = o.be16(12);
+        family = et == 0x0800u ? 4u : (et == 0x86DDu ? 6u : 0u);
+    }
+    const uint32_t L = v.L;
+    const uint32_t n = family && L < len ? len - L : 0u;
+    if (family == 4u && n >= 20u) {
+        // MutableIpv4Packet::new (ipv4.rs:540-566)
+        const uint32_t hl = (o.f.u8(L) & 15u) * 4u, total = o.be16(L + 2);
+        if (hl >= 20u && hl <= n && (total == 0u || total >= hl)) {
+            const uint32_t eff = total == 0u ? n : (total < n ? total : n);  // total_len, ipv4.rs:697-704
+            v.family = 4u;
+            v.hl = hl;
+            v.P = L + hl;
+            v.m = eff - hl;
+            v.proto = o.f.u8(L + 9);
+            v.l4 = v.proto == 17u || v.proto == 6u || v.proto == 1u;
+        }
+    } else if (family == 6u && n >= 40u) {  // MutableIpv6Packet::new: >= 40 B, payload = rest
+        v.family = 6u;
+        v.hl = 40u;
+        v.P = L + 40u;
+        v.m = n - 40u;
+        v.proto = o.f.u8(L + 6);
+        v.l4 = v.proto == 17u || v.proto == 6u || v.proto == 58u;
+    }
+    return v;
+}
+
+// The L4 view of a frame whose FrameViews has l4 set: whether its constructor
+// accepts the IP payload, and the byte offset of the checksum word in it.
+struct L4View {
+    bool view = false;
+    uint32_t sk = 0;  // skipword * 2
+};
+
+template <class O>
+NEXG_HD L4View l4_view(const O& o, const FrameViews& v) {
+    L4View q;
+    const uint32_t P = v.P, m = v.m;
+    if (v.proto == 17u) {  // MutableUdpPacket::new (udp.rs:101-121)
+        const uint32_t ul = m >= 8u ? o.be16(P + 4) : 0u;
+        q.view = m >= 8u && (ul == 0u || (ul >= 8u && ul <= m));
+        q.sk = 6;
+    } else if (v.proto == 6u) {  // MutableTcpPacket::new (tcp.rs:857-876)
+        const uint32_t hl = m >= 20u ? (o.f.u8(P + 12) >> 4) * 4u : 0u;
+        q.view = m >= 20u && hl >= 20u && hl <= m;
+        q.sk = 16;
+    } else {  // ICMP / ICMPv6: IcmpPacket::from_buf needs the 8-B header (icmp.rs:188-191)
+        q.view = m >= 8u;
+        q.sk = 2;
+    }
+    return q;
+}
+
+// util::checksum(raw[..header_len], 5) of the IPv4 view
+template <class O>
+NEXG_HD uint32_t ipv4_header_checksum(const O& o, const FrameViews& v) {
+    return fold_complement(o.wsum(v.L, v.L + 10) + o.wsum(v.L + 12, v.L + v.hl));
+}
+
+// the pseudo-header's address words (util.rs:91-93 / 135-137)
+template <class O>
+NEXG_HD uint64_t pseudo_addresses(const O& o, const FrameViews& v) {
+    const uint32_t L = v.L;
+    if (v.family == 4u) return (uint64_t)o.be16(L + 12) + o.be16(L + 14) + o.be16(L + 16) + o.be16(L + 18);
+    uint64_t pseudo = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 32; k += 2) pseudo += o.be16(L + 8 + k);
+    return pseudo;
+}
+
+// the L4 view's recompute_checksum over the whole payload_mut slice
+template <class O>
+NEXG_HD uint32_t l4_checksum(const O& o, const FrameViews& v, uint32_t sk, uint64_t pseudo) {
+    uint64_t t = o.wsum(v.P, v.P + sk) + o.wsum(v.P + sk + 2u, v.P + v.m);
+    if (v.proto != 1u) t += pseudo + v.proto + v.m;  // util.rs:89-97 / 119-127 (len as one u32)
+    return fold_complement(t);
+}
+
 // The mutable views' recompute_checksum chained over one frame f[0, len), in
 // place (nexg_fixup.hip's header names the reference's lines); returns the
 // frame's report row.
@@ -33,69 +139,22 @@ NEXG_HD nexg_fixup recompute_frame(uint8_t* f, uint32_t len, uint32_t opt_flags,
     nexg_fixup fx{0, 0, 0, 0, 0};
     const GlobalFrame gf{f};
     const FrameOps<GlobalFrame> o{gf, (uint32_t)(reinterpret_cast<uint64_t>(f) & 1u)};
-    // Ethernet view (ethernet.rs:355-361) or the raw IP packet at ip_offset
-    uint32_t L = 14, family = 0;
-    if (opt_flags & NEXG_PARSE_FROM_IP) {
-        L = ip_offset;
-        const uint32_t v = L < len ? (uint32_t)f[L] >> 4 : 0u;
-        family = v == 4u ? 4u : (v == 6u ? 6u : 0u);
-    } else if (len >= 14u) {
-        const uint32_t et = o.be16(12);
-        family = et == 0x0800u ? 4u : (et == 0x86DDu ? 6u : 0u);
+    const FrameViews v = frame_views(o, len, opt_flags, ip_offset);
+    if (v.family == 4u && (which & NEXG_FIX_IP)) {
+        const uint32_t c = ipv4_header_checksum(o, v);
+        put_be16(f + v.L + 10, c);
+        fx.done |= NEXG_FIX_IP;
+        fx.ip_csum = (uint16_t)c;
     }
-    const uint32_t n = family && L < len ? len - L : 0u;
-    uint32_t P = 0, m = 0, proto = 0;
-    uint64_t pseudo = 0;
-    bool l4 = false;
-    if (family == 4u && n >= 20u) {
-        // MutableIpv4Packet::new (ipv4.rs:540-566)
-        const uint32_t hl = ((uint32_t)f[L] & 15u) * 4u, total = o.be16(L + 2);
-        if (hl >= 20u && hl <= n && (total == 0u || total >= hl)) {
-            if (which & NEXG_FIX_IP) {  // util::checksum(raw[..header_len], 5)
-                const uint32_t c = fold_complement(o.wsum(L, L + 10) + o.wsum(L + 12, L + hl));
-                put_be16(f + L + 10, c);
-                fx.done |= NEXG_FIX_IP;
-                fx.ip_csum = (uint16_t)c;
-            }
-            const uint32_t eff = total == 0u ? n : (total < n ? total : n);  // total_len, ipv4.rs:697-704
-            P = L + hl;
-            m = eff - hl;
-            proto = f[L + 9];
-            pseudo = (uint64_t)o.be16(L + 12) + o.be16(L + 14) + o.be16(L + 16) + o.be16(L + 18);
-            l4 = proto == 17u || proto == 6u || proto == 1u;
-        }
-    } else if (family == 6u && n >= 40u) {  // MutableIpv6Packet::new: >= 40 B, payload = rest
-        P = L + 40;
-        m = n - 40u;
-        proto = f[L + 6];
-#pragma unroll
-        for (uint32_t k = 0; k < 32; k += 2) pseudo += o.be16(L + 8 + k);
-        l4 = proto == 17u || proto == 6u || proto == 58u;
-    }
-    if (l4 && (which & NEXG_FIX_L4)) {
-        uint32_t sk = 0;  // byte offset of the checksum word (skipword * 2)
-        bool view = false;
-        if (proto == 17u) {  // MutableUdpPacket::new (udp.rs:101-121)
-            const uint32_t ul = m >= 8u ? o.be16(P + 4) : 0u;
-            view = m >= 8u && (ul == 0u || (ul >= 8u && ul <= m));
-            sk = 6;
-        } else if (proto == 6u) {  // MutableTcpPacket::new (tcp.rs:857-876)
-            const uint32_t hl = m >= 20u ? ((uint32_t)f[P + 12] >> 4) * 4u : 0u;
-            view = m >= 20u && hl >= 20u && hl <= m;
-            sk = 16;
-        } else {  // ICMP / ICMPv6: IcmpPacket::from_buf needs the 8-B header (icmp.rs:188-191)
-            view = m >= 8u;
-            sk = 2;
-        }
-        if (view) {
-            uint64_t t = o.wsum(P, P + sk) + o.wsum(P + sk + 2u, P + m);
-            if (proto != 1u) t += pseudo + proto + m;  // util.rs:89-97 / 119-127 (len as one u32)
-            const uint32_t c = fold_complement(t);
-            put_be16(f + P + sk, c);
+    if (v.l4 && (which & NEXG_FIX_L4)) {
+        const L4View q = l4_view(o, v);
+        if (q.view) {
+            const uint32_t c = l4_checksum(o, v, q.sk, v.proto != 1u ? pseudo_addresses(o, v) : 0ull);
+            put_be16(f + v.P + q.sk, c);
             fx.done |= NEXG_FIX_L4;
-            fx.proto = (uint8_t)proto;
+            fx.proto = (uint8_t)v.proto;
             fx.l4_csum = (uint16_t)c;
-            fx.l4_off = (uint16_t)P;
+            fx.l4_off = (uint16_t)v.P;
         }
     }
     return fx;

@@ -11,6 +11,7 @@
 
 #include "match_core.hpp"
 #include "nexg_internal.hpp"
+#include "rewrite_core.hpp"
 
 struct nexg_ctx {
     int device;
@@ -262,6 +263,23 @@ int nexg_recompute_checksums_batch(nexg_ctx* ctx, const nexg_frames* frames, con
     DeviceGuard g(ctx);
     const nexg::ParseArgs a = parse_args(frames, option);
     return launched(ctx, nexg::launch_recompute(a, which, out, as_stream(stream)));
+}
+
+int nexg_actions_check(const nexg_actions* actions) {
+    return nexg::check_actions(actions) ? NEXG_EINVAL : NEXG_OK;
+}
+
+int nexg_rewrite_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_parse_option* option,
+                       const nexg_actions* actions, const uint8_t* action_index, nexg_rewritten* out, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    if (!option) return fail(ctx, NEXG_EINVAL, "rewrite: NULL option%s", nullptr);
+    if (const char* why = nexg::check_actions(actions)) return fail(ctx, NEXG_EINVAL, "rewrite: %s", why);
+    if (misaligned(7u, out)) return fail(ctx, NEXG_EINVAL, "misaligned output%s", nullptr);
+    if (frames->count == 0) return NEXG_OK;
+    DeviceGuard g(ctx);
+    const nexg::ParseArgs a = parse_args(frames, option);
+    return launched(ctx, nexg::launch_rewrite(a, *actions, action_index, out, as_stream(stream)));
 }
 
 int nexg_checksum_batch(nexg_ctx* ctx, const nexg_frames* bufs, uint32_t skipword, uint16_t* out,

@@ -98,6 +98,10 @@ hipError_t launch_sparse_expand(const ParseArgs& a, const uint8_t* sparse, nexg_
 
 hipError_t launch_recompute(const ParseArgs& a, uint32_t which, nexg_fixup* out, hipStream_t s);
 
+// nexg_rewrite_batch (nexg_rewrite.hip); `actions` has passed check_actions (rewrite_core.hpp)
+hipError_t launch_rewrite(const ParseArgs& a, const nexg_actions& actions, const uint8_t* action_index,
+                          nexg_rewritten* out, hipStream_t s);
+
 hipError_t launch_decode_options(const ParseArgs& a, const nexg_record* recs, nexg_options* out,
                                  hipStream_t s);
 

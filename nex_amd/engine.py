@@ -284,6 +284,33 @@ class Engine:
                                                             _ptr(out), self._stream(stream)))
         return out
 
+    def rewrite(self, batch: FrameBatch, actions, index=None, option: ParseOption = ParseOption(), report=True,
+                stream=None):
+        """Header fields rewritten in place in batch.data (nexg_rewrite_batch):
+        the mutable setters under ChecksumMode::Automatic — MACs, IPv4 / IPv6
+        addresses, ports, TTL / hop limit, TOS / traffic class — with the
+        checksums they dirty recomputed, or updated by RFC 1624 with
+        ActionSet(incremental=True). `actions` is a nex_amd.rewrite.ActionSet,
+        `index` a uint8 device tensor with one action number per frame
+        (abi.ACTION_NONE or any number past the set: leave the frame alone) or
+        None (action 0 for every frame). Returns the nexg_rewritten[count]
+        rows (uint8 device tensor, abi.REWRITTEN_DTYPE) or None. One kernel,
+        no synchronisation.
+
+        The recipe, a match-action table: rule j of the filter gets action j.
+
+            rec = eng.parse(batch, out_kind=abi.OUT_RECORD)
+            idx, sel, rule = eng.select(batch, rec, flt, want_rule=True)
+            eng.rewrite(sel, actions, rule)
+        """
+        torch = _torch()
+        ac = actions.to_c()  # ValueError for what nexg_rewrite_batch rejects
+        out = torch.empty(max(batch.count, 1) * 8, dtype=torch.uint8, device=self.torch_device) if report else None
+        opt = abi.ParseOptionC(option.flags(ParseMode.Lenient), option.offset)
+        self._check(self.lib.nexg_rewrite_batch(self.ctx, _frames(batch), ctypes.byref(opt), ctypes.byref(ac),
+                                                _ptr(index), _ptr(out), self._stream(stream)))
+        return out[: batch.count * 8] if report else None
+
     def decode_options(self, batch: FrameBatch, records, stream=None):
         """Ipv4Header.options / TcpHeader.options of every frame as positions
         (nexg_decode_options; ipv4.rs:442-508, tcp.rs:767-818). `records` is
