@@ -622,6 +622,136 @@ static inline uint64_t nexg_decap_select_workspace(uint64_t count) {
     return 4u * ((tiles + 255u) / 256u * 256u) + 16u;
 }
 
+/* ---- tunnel encapsulation (VXLAN, GRE; extension) -----------------------------
+ * The other direction of the section above: every frame of a table is copied
+ * into a new buffer behind an outer Ethernet / IPv4 or IPv6 / UDP + VXLAN or GRE
+ * header, the bytes the reference's builders give when composed as
+ * examples/udp_ping.rs composes them: EthernetPacketBuilder(Ipv4PacketBuilder
+ * or Ipv6PacketBuilder(UdpPacketBuilder(VxlanPacket::to_bytes))), vxlan.rs:73-84,
+ * and for GRE the IP builder with protocol 47 around GrePacket::to_bytes,
+ * gre.rs:115-160. Up to 16 tunnel specs per call; tunnel_index[i] (device
+ * memory, one byte per frame, usually the out_rule of nexg_select_batch: rule j
+ * gets tunnel j) picks frame i's, NULL means spec 0 for every frame. Two calls,
+ * as the gather: nexg_encap_plan lays the outputs out, the host reads the
+ * total and allocates, nexg_encap_frames fills.
+ *
+ * Per frame i, in this order:
+ *  1 spec     t = tunnel_index ? tunnel_index[i] : 0. An extent that leaves
+ *             [0, data_bytes) or a length above 65535 (the gather's rule):
+ *             output length 0, status NEXG_ERR_BAD_EXTENT, row.tunnel = t.
+ *             t >= n_tunnels: a pass-through, the frame copied unchanged, row
+ *             {0, NEXG_TUNNEL_NONE, 0, 0, 0, 0}; the index never reaches past
+ *             the set.
+ *  2 payload  VXLAN, and GRE without NEXG_ENCAP_GRE_L3: the whole frame,
+ *             protocol_type 0x6558. GRE_L3 with len < 14: status
+ *             NEXG_ERR_BUFFER_TOO_SHORT, output length 0; otherwise
+ *             protocol_type = the big-endian u16 at bytes 12..13, whatever its
+ *             value, and the payload is bytes [14, len). m = the payload's
+ *             length.
+ *  3 length   H = 14 + (20 | 40) + (VXLAN: 8 + 8 | GRE: 4 + 4 K + 4 S).
+ *             H + m > 65535: status NEXG_ERR_INVALID_LENGTH, output length 0
+ *             (an outer frame is itself a valid nexg_frames entry). Otherwise
+ *             the output length is H + m.
+ *  4 header   Ethernet: eth_dst, eth_src, 0x0800 / 0x86DD. IPv4: IHL 5, byte 1
+ *             = tos, total length H - 14 + m, identification ip_id, ip_flags in
+ *             the top 3 bits of word 3, fragment offset 0, ttl, protocol 17 /
+ *             47, the header checksum of ipv4::checksum. IPv6: traffic class
+ *             tos, flow_label, payload_length H - 54 + m, next header 17 / 47,
+ *             hop limit ttl. UDP: src_port (+ flows[i].hash % port_span under
+ *             NEXG_ENCAP_FLOW_PORT, RFC 7348's entropy), dst_port (0: 4789),
+ *             length 16 + m, checksum 0, or under NEXG_ENCAP_UDP_CSUM
+ *             udp::checksum over the pseudo-header, the UDP header, the VXLAN
+ *             header and the payload; a computed 0 stays 0.
+ *             VXLAN: 08 00 00 00 vni[3] 00. GRE: K << 13 | S << 12 (version 0,
+ *             no C / R bit), protocol_type, the key (K), seq_base + i mod 2^32
+ *             (S; i is the frame's index in the table).
+ *  5 pads     the bytes from the frame's end up to out_offsets[i + 1] are
+ *             zero (fewer than 16 with the plan's offsets; at most 15 are
+ *             written).
+ * Out of scope: Geneve, NVGRE, the GRE checksum and routing, fragmentation to
+ * an MTU, outer VLAN tags, an incrementing IPv4 id, fixing inner checksums;
+ * nested encapsulation is the pass run twice. */
+#define NEXG_ENCAP_VXLAN 1
+#define NEXG_ENCAP_GRE 2
+#define NEXG_ENCAP_UDP_CSUM  0x01u /* VXLAN: compute the outer UDP checksum (default: field 0) */
+#define NEXG_ENCAP_FLOW_PORT 0x02u /* VXLAN: src port = src_port + flows[i].hash % port_span */
+#define NEXG_ENCAP_GRE_KEY   0x04u /* GRE: K bit, key = id */
+#define NEXG_ENCAP_GRE_SEQ   0x08u /* GRE: S bit, sequence = seq_base + i (mod 2^32), i the frame's index in the table */
+#define NEXG_ENCAP_GRE_L3    0x10u /* GRE: drop the inner Ethernet header; protocol_type = its EtherType */
+#define NEXG_ENCAP_MAX_TUNNELS 16
+#define NEXG_TUNNEL_NONE 0xFFu
+typedef struct nexg_tunnel_spec {   /* 96 bytes */
+    uint8_t kind;                   /* NEXG_ENCAP_VXLAN / _GRE */
+    uint8_t family;                 /* outer IP: 4 or 6 */
+    uint8_t ttl;                    /* IPv4 ttl / IPv6 hop limit */
+    uint8_t tos;                    /* IPv4 byte 1 / IPv6 traffic class */
+    uint32_t flags;                 /* NEXG_ENCAP_* */
+    uint8_t eth_dst[6], eth_src[6];
+    uint8_t src[16], dst[16];       /* network order; family 4 uses the first 4 bytes */
+    uint16_t src_port, dst_port;    /* VXLAN; dst_port 0 means 4789 */
+    uint16_t port_span;             /* FLOW_PORT: 1..65536-src_port; else 0 */
+    uint16_t ip_id;                 /* IPv4 identification */
+    uint32_t id;                    /* VXLAN vni (24 bits) / GRE key */
+    uint32_t seq_base;
+    uint32_t flow_label;            /* IPv6, 20 bits */
+    uint8_t ip_flags;               /* IPv4, 3 bits (DF = 2) */
+    uint8_t reserved[23];           /* must be 0 */
+} nexg_tunnel_spec;
+typedef struct nexg_tunnels {       /* host memory, read during the call only */
+    uint32_t n_tunnels, reserved;
+    nexg_tunnel_spec tunnels[NEXG_ENCAP_MAX_TUNNELS];
+} nexg_tunnels;
+typedef struct nexg_encapped {      /* 8 bytes */
+    uint8_t status;                 /* NEXG_FRAME_OK / NEXG_ERR_* */
+    uint8_t tunnel;                 /* the spec used, NEXG_TUNNEL_NONE for a pass-through */
+    uint8_t hdr_len;                /* bytes put before the payload (0 for pass-through / error) */
+    uint8_t reserved;
+    uint16_t src_port, l4_csum;     /* VXLAN: the values written; else 0 */
+} nexg_encapped;
+struct nexg_flow; /* the rows of nexg_flow_batch, declared with the flow section below */
+
+/* Host only. NEXG_EINVAL: n_tunnels 0 or above 16; an unknown kind or family;
+ * unknown flag bits; a VXLAN flag (UDP_CSUM, FLOW_PORT) on a GRE spec or a GRE
+ * flag on a VXLAN spec; a VXLAN id above 24 bits; flow_label above 20 bits;
+ * ip_flags above 7; FLOW_PORT with port_span 0 or src_port + port_span >
+ * 65536; port_span != 0 without FLOW_PORT; a nonzero reserved field. */
+int nexg_tunnels_check(const nexg_tunnels* set);
+
+/* out_offsets[i] (count + 1 entries, 8-B aligned) = the sum over j < i of
+ * frame j's output length rounded up to `align` (1, 4, 8 or 16);
+ * out_offsets[count] = the total; out_len[i] (optional) = the output length.
+ * workspace: as the gather plan's (8-B aligned). count <= 2^32 - 1; count == 0
+ * writes out_offsets[0] = 0 and launches nothing else. Scans only, no atomics.
+ * Three kernels on `stream`. */
+int nexg_encap_plan(nexg_ctx* ctx, const nexg_frames* frames, const nexg_tunnels* set, const uint8_t* tunnel_index,
+                    uint32_t align, uint64_t* out_offsets, uint32_t* out_len, void* workspace, uint64_t workspace_bytes,
+                    void* stream);
+static inline uint64_t nexg_encap_plan_workspace(uint64_t count) {
+    const uint64_t tiles = (count + 255u) / 256u;
+    return 8u * ((tiles + 255u) / 256u * 256u) + 16u;
+}
+
+/* Frame i's outer frame at out_data (16-B aligned) + out_offsets[i], the pads
+ * zero; rows[i] (optional, 8-B aligned) says what was written. flows: the rows
+ * of nexg_flow_batch over the same table (8-B aligned), needed when a spec has
+ * NEXG_ENCAP_FLOW_PORT (NEXG_EINVAL when NULL then and count > 0), else ignored. No store
+ * lands at or past out_cap or outside [out_offsets[i], out_offsets[i + 1]),
+ * whatever out_offsets holds (it is caller memory), and the output is never
+ * read. Source reads follow the 16-B block rule and never leave a frame's
+ * blocks; the inner bytes are read once, the UDP checksum summed from the
+ * loads that feed the copy. A frame cut short by out_cap or by an
+ * out_offsets[i + 1] below its end has its bytes below the cut, but its UDP
+ * checksum field and rows[i].l4_csum are undefined under NEXG_ENCAP_UDP_CSUM
+ * (the sum covers what was copied). Deterministic, no atomics, no workspace.
+ * NEXG_EINVAL also for a NULL out_offsets with count > 0, a NULL out_data with
+ * out_cap > 0, a misaligned pointer, count > 2^32 - 1. count == 0 launches
+ * nothing. With align 1, {out_data, total, out_offsets} is a packed batch;
+ * with a larger align, {out_data, total, out_offsets, out_len} an offsets +
+ * lengths batch (monotone). One kernel on `stream`. */
+int nexg_encap_frames(nexg_ctx* ctx, const nexg_frames* frames, const nexg_tunnels* set, const uint8_t* tunnel_index,
+                      const struct nexg_flow* flows, const uint64_t* out_offsets, uint8_t* out_data, uint64_t out_cap,
+                      nexg_encapped* rows, void* stream);
+
 /* ---- DNS messages ------------------------------------------------------------
  * Frame::try_from_buf stops at the UDP header; the reference's DNS parser
  * DnsPacket::try_from_buf (dns.rs:1166-1259) reads Frame.payload, as its

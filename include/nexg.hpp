@@ -37,6 +37,11 @@
  *                           MutableIpv4Packet, MutableIpv6Packet, MutableTcpPacket,
  *                           MutableUdpPacket; examples/mutable_chaining.rs) on
  *                           a batch in place, one action per filter rule
+ *   Tunnel, TunnelSet, Engine::encap_plan / encap / encap_bufs
+ *                           VxlanPacket::to_bytes (vxlan.rs:73-84) and
+ *                           GrePacket::to_bytes (gre.rs:115-160) inside the
+ *                           Ethernet / IP / UDP builders, around every frame
+ *                           of a batch, one tunnel per filter rule
  *   FlowOption, Engine::flow / flow_partition / flow_bufs
  *                           no reference counterpart (an extension): the
  *                           Toeplitz RSS hash of every frame's flow key and the
@@ -1172,6 +1177,92 @@ class ActionSet {
     }
 };
 
+/* ---- tunnel encapsulation (VXLAN, GRE) ------------------------------------------- */
+
+// Builder of one nexg_tunnel_spec (include/nexg.h). Addresses in network
+// order: 4 bytes (family 4) or 16 (family 6).
+//   Tunnel::vxlan(4, src, dst, 5001).macs(next_hop, mine).ports(49152, 0, 16384).udp_csum()
+//   Tunnel::gre(6, src, dst).key(7).l3()
+class Tunnel {
+   public:
+    nexg_tunnel_spec t{};
+
+    static Tunnel vxlan(uint8_t family, const uint8_t* src, const uint8_t* dst, uint32_t vni) {
+        Tunnel x(NEXG_ENCAP_VXLAN, family, src, dst);
+        x.t.id = vni;
+        return x;
+    }
+    static Tunnel gre(uint8_t family, const uint8_t* src, const uint8_t* dst) { return Tunnel(NEXG_ENCAP_GRE, family, src, dst); }
+    Tunnel& macs(const uint8_t dst[6], const uint8_t src[6]) {
+        memcpy(t.eth_dst, dst, 6);
+        memcpy(t.eth_src, src, 6);
+        return *this;
+    }
+    // VXLAN: the UDP ports (dst 0: 4789); span > 0: source port = src + flow hash % span (NEXG_ENCAP_FLOW_PORT)
+    Tunnel& ports(uint16_t src, uint16_t dst = 0, uint16_t span = 0) {
+        t.src_port = src;
+        t.dst_port = dst;
+        t.port_span = span;
+        t.flags = span ? t.flags | NEXG_ENCAP_FLOW_PORT : t.flags & ~NEXG_ENCAP_FLOW_PORT;
+        return *this;
+    }
+    Tunnel& udp_csum(bool on = true) { return flag(NEXG_ENCAP_UDP_CSUM, on); }
+    Tunnel& key(uint32_t k) {
+        t.id = k;
+        return flag(NEXG_ENCAP_GRE_KEY, true);
+    }
+    Tunnel& sequence(uint32_t base) {
+        t.seq_base = base;
+        return flag(NEXG_ENCAP_GRE_SEQ, true);
+    }
+    Tunnel& l3(bool on = true) { return flag(NEXG_ENCAP_GRE_L3, on); }
+    Tunnel& ip(uint8_t ttl, uint8_t tos = 0, uint16_t ip_id = 0, uint8_t ip_flags = 0, uint32_t flow_label = 0) {
+        t.ttl = ttl;
+        t.tos = tos;
+        t.ip_id = ip_id;
+        t.ip_flags = ip_flags;
+        t.flow_label = flow_label;
+        return *this;
+    }
+
+   private:
+    Tunnel(uint8_t kind, uint8_t family, const uint8_t* src, const uint8_t* dst) {
+        if (family != 4 && family != 6) throw Error("Tunnel: an address family is 4 or 6");
+        t.kind = kind;
+        t.family = family;
+        t.ttl = 64;
+        memcpy(t.src, src, family == 4 ? 4 : 16);
+        memcpy(t.dst, dst, family == 4 ? 4 : 16);
+    }
+    Tunnel& flag(uint32_t bit, bool on) {
+        t.flags = on ? t.flags | bit : t.flags & ~bit;
+        return *this;
+    }
+};
+
+// Builder of a nexg_tunnels: up to 16 specs. add throws nexg::Error for the
+// 17th, get() where nexg_encap_plan would return NEXG_EINVAL.
+class TunnelSet {
+   public:
+    nexg_tunnels s{};
+
+    TunnelSet& add(const Tunnel& tunnel) {
+        if (s.n_tunnels >= NEXG_ENCAP_MAX_TUNNELS) throw Error("TunnelSet: more than 16 tunnels");
+        s.tunnels[s.n_tunnels++] = tunnel.t;
+        return *this;
+    }
+    bool needs_flows() const {
+        for (uint32_t i = 0; i < s.n_tunnels && i < NEXG_ENCAP_MAX_TUNNELS; i++)
+            if (s.tunnels[i].flags & NEXG_ENCAP_FLOW_PORT) return true;
+        return false;
+    }
+    // the set, checked as nexg_encap_plan checks it
+    const nexg_tunnels& get() const {
+        if (nexg_tunnels_check(&s) != NEXG_OK) throw Error("TunnelSet: not a valid nexg_tunnels (include/nexg.h)");
+        return s;
+    }
+};
+
 /* ---- the engine --------------------------------------------------------- */
 
 // The calling thread's current device switched for a scope and restored after
@@ -2080,6 +2171,87 @@ class Engine {  // one nexg context on one gfx950 device, one stream
         for (uint64_t i = 0; i < n; i++)
             std::copy(data.begin() + hb.offs[i], data.begin() + hb.offs[i] + hb.lens[i], frames[i].begin());
         return rows;
+    }
+
+    // Where encap puts each frame's outer frame (nexg_encap_plan): out_offsets
+    // holds frames.count + 1 entries, out_len (may be null) frames.count;
+    // tunnel_index: a device array with one tunnel number per frame (the
+    // out_rule of select: rule j gets tunnel j; NEXG_TUNNEL_NONE copies a frame
+    // unchanged) or null (tunnel 0 for all). Returns the total bytes (one
+    // stream synchronisation) to allocate for encap.
+    uint64_t encap_plan(const nexg_frames& frames, const TunnelSet& tunnels, const uint8_t* tunnel_index, uint32_t align,
+                        uint64_t* out_offsets, uint32_t* out_len) {
+        DeviceScope ds(device_);
+        const uint64_t wsb = nexg_encap_plan_workspace(frames.count);
+        void* ws = scratch(48, wsb);
+        check(nexg_encap_plan(ctx_, &frames, &tunnels.get(), tunnel_index, align, out_offsets, out_len, ws, wsb, stream_),
+              "nexg_encap_plan");
+        uint64_t total = 0;
+        check_hip(hipMemcpyAsync(&total, out_offsets + frames.count, 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        return total;
+    }
+
+    // Every frame behind its tunnel's outer Ethernet / IP / UDP + VXLAN or GRE
+    // header at out_data + out_offsets[i], pads zero, nothing at or past
+    // out_cap (nexg_encap_frames; VxlanPacket::to_bytes vxlan.rs:73-84,
+    // GrePacket::to_bytes gre.rs:115-160 inside the reference's builders).
+    // flows: the rows of flow() over the same table, needed when a tunnel
+    // takes its source port from the flow hash; rows: a device array of
+    // frames.count nexg_encapped (8-B aligned) or null.
+    void encap(const nexg_frames& frames, const TunnelSet& tunnels, const uint8_t* tunnel_index, const nexg_flow* flows,
+               const uint64_t* out_offsets, uint8_t* out_data, uint64_t out_cap, nexg_encapped* rows = nullptr) {
+        DeviceScope ds(device_);
+        check(nexg_encap_frames(ctx_, &frames, &tunnels.get(), tunnel_index, flows, out_offsets, out_data, out_cap, rows,
+                                stream_),
+              "nexg_encap_frames");
+    }
+
+    // encap of host frames: index: one tunnel number per frame, or empty
+    // (tunnel 0 for all). With a tunnel that takes its source port from the
+    // flow hash the frames are parsed (NEXG_OUT_RECORD) and hashed first. The
+    // outer frames lie in `data` at offsets[i], lengths[i] bytes each (each
+    // start rounded up to `align`).
+    struct Encapped {
+        std::vector<nexg_encapped> rows;
+        std::vector<uint64_t> offsets;  // rows.size() + 1
+        std::vector<uint32_t> lengths;
+        std::vector<uint8_t> data;
+    };
+    Encapped encap_bufs(const std::vector<std::vector<uint8_t>>& frames, const TunnelSet& tunnels,
+                        const std::vector<uint8_t>& index = {}, uint32_t align = 1, ParseOption option = {}) {
+        DeviceScope ds(device_);
+        const uint64_t n = frames.size();
+        Encapped out;
+        out.offsets.assign(1, 0);
+        if (!index.empty() && index.size() != n) throw Error("encap_bufs: one tunnel number per frame");
+        (void)tunnels.get();
+        if (n == 0) return out;
+        HostBatch hb(*this, frames);
+        const uint8_t* d_index = index.empty() ? nullptr : static_cast<const uint8_t*>(upload(47, index.data(), n));
+        nexg_flow* d_flows = nullptr;
+        if (tunnels.needs_flows()) {
+            nexg_record* d_recs = static_cast<nexg_record*>(scratch(3, n * 64));
+            d_flows = static_cast<nexg_flow*>(scratch(49, n * sizeof(nexg_flow)));
+            parse(hb.fb, option, ParseMode::Lenient, NEXG_OUT_RECORD, d_recs);
+            check(nexg_flow_batch(ctx_, &hb.fb, d_recs, nullptr, d_flows, stream_), "nexg_flow_batch");
+        }
+        uint64_t* d_off = static_cast<uint64_t*>(scratch(50, (n + 1) * 8));
+        uint32_t* d_len = static_cast<uint32_t*>(scratch(51, n * 4));
+        nexg_encapped* d_rows = static_cast<nexg_encapped*>(scratch(52, n * sizeof(nexg_encapped)));
+        const uint64_t total = encap_plan(hb.fb, tunnels, d_index, align, d_off, d_len);
+        uint8_t* d_data = static_cast<uint8_t*>(scratch(53, total));
+        encap(hb.fb, tunnels, d_index, d_flows, d_off, d_data, total, d_rows);
+        out.rows.resize(n);
+        out.offsets.resize(n + 1);
+        out.lengths.resize(n);
+        out.data.resize(total);
+        check_hip(hipMemcpyAsync(out.rows.data(), d_rows, n * sizeof(nexg_encapped), hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipMemcpyAsync(out.offsets.data(), d_off, (n + 1) * 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipMemcpyAsync(out.lengths.data(), d_len, n * 4, hipMemcpyDeviceToHost, stream_), "D2H");
+        if (total) check_hip(hipMemcpyAsync(out.data.data(), d_data, total, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        return out;
     }
 
    private:

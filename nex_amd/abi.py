@@ -413,6 +413,43 @@ def decap_select_workspace(count):
     return 4 * ((tiles + 255) // 256 * 256) + 16
 
 
+# tunnel encapsulation (nexg_encap_plan / nexg_encap_frames; an extension: the
+# reference builds one packet at a time)
+ENCAP_VXLAN, ENCAP_GRE = 1, 2
+ENCAP_UDP_CSUM, ENCAP_FLOW_PORT, ENCAP_GRE_KEY, ENCAP_GRE_SEQ, ENCAP_GRE_L3 = 0x01, 0x02, 0x04, 0x08, 0x10
+ENCAP_VXLAN_FLAGS = ENCAP_UDP_CSUM | ENCAP_FLOW_PORT
+ENCAP_GRE_FLAGS = ENCAP_GRE_KEY | ENCAP_GRE_SEQ | ENCAP_GRE_L3
+ENCAP_MAX_TUNNELS = 16
+TUNNEL_NONE = 0xFF
+ENCAPPED_DTYPE = np.dtype([("status", "u1"), ("tunnel", "u1"), ("hdr_len", "u1"), ("reserved", "u1"),
+                           ("src_port", "<u2"), ("l4_csum", "<u2")])
+assert ENCAPPED_DTYPE.itemsize == 8
+
+
+class TunnelSpecC(ctypes.Structure):
+    """struct nexg_tunnel_spec"""
+    _fields_ = [("kind", ctypes.c_uint8), ("family", ctypes.c_uint8), ("ttl", ctypes.c_uint8), ("tos", ctypes.c_uint8),
+                ("flags", ctypes.c_uint32), ("eth_dst", ctypes.c_uint8 * 6), ("eth_src", ctypes.c_uint8 * 6),
+                ("src", ctypes.c_uint8 * 16), ("dst", ctypes.c_uint8 * 16), ("src_port", ctypes.c_uint16),
+                ("dst_port", ctypes.c_uint16), ("port_span", ctypes.c_uint16), ("ip_id", ctypes.c_uint16),
+                ("id", ctypes.c_uint32), ("seq_base", ctypes.c_uint32), ("flow_label", ctypes.c_uint32),
+                ("ip_flags", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 23)]
+
+
+class TunnelsC(ctypes.Structure):
+    """struct nexg_tunnels"""
+    _fields_ = [("n_tunnels", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("tunnels", TunnelSpecC * ENCAP_MAX_TUNNELS)]
+
+
+assert ctypes.sizeof(TunnelSpecC) == 96 and ctypes.sizeof(TunnelsC) == 8 + 16 * 96
+
+
+def encap_plan_workspace(count):
+    """nexg_encap_plan_workspace: bytes of nexg_encap_plan's workspace (the gather plan's)."""
+    return gather_plan_workspace(count)
+
+
 # DNS messages (nexg_dns_batch / nexg_dns_entries)
 DNS_ANY_UDP = 0x1
 DNS_PORT = 53  # what nexg_dns_option.port = 0 means
@@ -602,7 +639,8 @@ def flow_table_workspace(n_in, n_groups):
 #: static inline helpers of include/nexg.h (header-only, not exported)
 HEADER_INLINE = ("nexg_sparse_decode", "nexg_grouped_code", "nexg_grouped_exc_slot", "nexg_offsets32_bases",
                  "nexg_offsets32_bytes", "nexg_decap_select_workspace", "nexg_dns_tile_first_bytes",
-                 "nexg_select_workspace", "nexg_match_select_workspace", "nexg_gather_plan_workspace", "nexg_flow_partition_workspace",
+                 "nexg_select_workspace", "nexg_match_select_workspace", "nexg_gather_plan_workspace", "nexg_encap_plan_workspace",
+                 "nexg_flow_partition_workspace",
                  "nexg_flow_sort_workspace", "nexg_flow_groups_workspace", "nexg_flow_table_workspace")
 
 #: every symbol include/nexg.h declares (tests check the .so exports them)
@@ -613,6 +651,7 @@ EXPORTED_SYMBOLS = (
     "nexg_filter_check", "nexg_select_batch", "nexg_gather_plan", "nexg_gather_frames", "nexg_gather_rows",
     "nexg_patterns_check", "nexg_match_batch", "nexg_match_select",
     "nexg_actions_check", "nexg_rewrite_batch",
+    "nexg_tunnels_check", "nexg_encap_plan", "nexg_encap_frames",
     "nexg_flow_batch", "nexg_flow_partition", "nexg_flow_sort", "nexg_flow_groups",
     "nexg_flow_table_merge",
     "nexg_probe_span_clock", "nexg_probe_latency",

@@ -9,6 +9,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "encap_core.hpp"
 #include "match_core.hpp"
 #include "nexg_internal.hpp"
 #include "rewrite_core.hpp"
@@ -483,6 +484,55 @@ int nexg_gather_frames(nexg_ctx* ctx, const nexg_frames* sel, const uint64_t* ou
     const nexg::ParseArgs a = to_args(sel);
     DeviceGuard g(ctx);
     return launched(ctx, nexg::launch_gather_frames(a, out_offsets, out_data, out_cap, as_stream(stream)));
+}
+
+int nexg_tunnels_check(const nexg_tunnels* set) { return nexg::check_tunnels(set) ? NEXG_EINVAL : NEXG_OK; }
+
+int nexg_encap_plan(nexg_ctx* ctx, const nexg_frames* frames, const nexg_tunnels* set, const uint8_t* tunnel_index,
+                    uint32_t align, uint64_t* out_offsets, uint32_t* out_len, void* workspace, uint64_t workspace_bytes,
+                    void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    if (const char* why = nexg::check_tunnels(set)) return fail(ctx, NEXG_EINVAL, "encap_plan: %s", why);
+    if (align != 1 && align != 4 && align != 8 && align != 16)
+        return fail(ctx, NEXG_EINVAL, "encap_plan: align must be 1, 4, 8 or 16%s", nullptr);
+    const uint64_t count = frames->count;
+    if (int rc = check_count(ctx, "encap_plan", count)) return rc;
+    if (!out_offsets) return fail(ctx, NEXG_EINVAL, "NULL out_offsets%s", nullptr);
+    if (count && !workspace) return fail(ctx, NEXG_EINVAL, "NULL workspace%s", nullptr);
+    if (int rc = check_workspace(ctx, "encap_plan", count, workspace_bytes, nexg_encap_plan_workspace(count))) return rc;
+    if (misaligned(7u, out_offsets, workspace) || misaligned(3u, out_len))
+        return fail(ctx, NEXG_EINVAL, "misaligned output or workspace%s", nullptr);
+    nexg::EncapSet es;
+    nexg::prepare_tunnels(*set, es);
+    const nexg::ParseArgs a = to_args(frames);
+    DeviceGuard g(ctx);
+    return launched(ctx, nexg::launch_encap_plan(a, es, tunnel_index, align, out_offsets, out_len,
+                                                 static_cast<uint64_t*>(workspace), as_stream(stream)));
+}
+
+int nexg_encap_frames(nexg_ctx* ctx, const nexg_frames* frames, const nexg_tunnels* set, const uint8_t* tunnel_index,
+                      const nexg_flow* flows, const uint64_t* out_offsets, uint8_t* out_data, uint64_t out_cap,
+                      nexg_encapped* rows, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    if (const char* why = nexg::check_tunnels(set)) return fail(ctx, NEXG_EINVAL, "encap_frames: %s", why);
+    if (int rc = check_count(ctx, "encap_frames", frames->count)) return rc;
+    if (!flows && frames->count)
+        for (uint32_t i = 0; i < set->n_tunnels; i++)
+            if (set->tunnels[i].flags & NEXG_ENCAP_FLOW_PORT)
+                return fail(ctx, NEXG_EINVAL, "encap_frames: a spec has FLOW_PORT and flows is NULL%s", nullptr);
+    if (frames->count && !out_offsets) return fail(ctx, NEXG_EINVAL, "NULL out_offsets%s", nullptr);
+    if (out_cap && !out_data) return fail(ctx, NEXG_EINVAL, "NULL out_data with a nonzero capacity%s", nullptr);
+    if (misaligned(7u, out_offsets, flows, rows) || misaligned(15u, out_data))
+        return fail(ctx, NEXG_EINVAL, "misaligned out_offsets, flows, rows or out_data%s", nullptr);
+    if (frames->count == 0) return NEXG_OK;
+    nexg::EncapSet es;
+    nexg::prepare_tunnels(*set, es);
+    const nexg::ParseArgs a = to_args(frames);
+    DeviceGuard g(ctx);
+    return launched(ctx, nexg::launch_encap_frames(a, es, tunnel_index, flows, out_offsets, out_data, out_cap, rows,
+                                                   as_stream(stream)));
 }
 
 int nexg_gather_rows(nexg_ctx* ctx, const void* rows, uint32_t row_bytes, uint64_t rows_count,

@@ -114,6 +114,17 @@ hipError_t launch_decap_select(const nexg_tunnel* tunnels, const uint64_t* inner
                                uint64_t count, uint32_t inner_mask, uint32_t* out_index, uint64_t* out_off,
                                uint32_t* out_len, uint64_t* out_count, uint32_t* tile_count, hipStream_t s);
 
+// nexg_encap_plan / nexg_encap_frames (nexg_encap.hip). The specs travel as a
+// kernel argument in the form encap_core.hpp's prepare_tunnels gives them.
+// tile_sum: one u64 per 256-frame tile (the caller's workspace), left holding
+// the tiles' exclusive scan.
+struct EncapSet;
+hipError_t launch_encap_plan(const ParseArgs& a, const EncapSet& set, const uint8_t* tunnel_index, uint32_t align,
+                             uint64_t* out_offsets, uint32_t* out_len, uint64_t* tile_sum, hipStream_t s);
+hipError_t launch_encap_frames(const ParseArgs& a, const EncapSet& set, const uint8_t* tunnel_index, const nexg_flow* flows,
+                               const uint64_t* out_offsets, uint8_t* out_data, uint64_t out_cap, nexg_encapped* rows,
+                               hipStream_t s);
+
 // nexg_dns_batch / nexg_dns_entries (nexg_dns.hip). tile_first: one u64 per
 // 256-frame tile + 1, left holding the tiles' exclusive scan and the total.
 hipError_t launch_dns(const ParseArgs& a, const nexg_record* recs, uint32_t any_udp, uint32_t port, nexg_dns* out,

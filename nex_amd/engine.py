@@ -505,6 +505,61 @@ class Engine:
         return FrameBatch(data=data[:total], count=n, offsets=offs, lengths=None if ln is None else ln[:n],
                           hints=0 if ln is None else abi.FRAMES_MONOTONE)
 
+    def encap(self, batch: FrameBatch, tunnels, index=None, flows=None, align: int = 1, report=True, stream=None):
+        """Every frame of `batch` copied into a new buffer behind an outer
+        Ethernet / IP / UDP + VXLAN or GRE header (nexg_encap_plan +
+        nexg_encap_frames): the bytes the reference's builders give around
+        VxlanPacket::to_bytes / GrePacket::to_bytes. `tunnels` is a
+        nex_amd.encap.TunnelSet, `index` a uint8 device tensor with one tunnel
+        number per frame (abi.TUNNEL_NONE or any number past the set: the
+        frame is copied unchanged) or None (tunnel 0 for every frame), `flows`
+        the rows Engine.flow gave for the same table, needed when a spec
+        takes its UDP source port from the flow hash. Returns (FrameBatch,
+        rows): the batch owns its data, packed (offsets only) with align 1,
+        offsets + lengths with each frame's start rounded up to `align` (4, 8
+        or 16) and the pads zero; rows is the nexg_encapped[count] report
+        (uint8 device tensor, abi.ENCAPPED_DTYPE) or None. A frame that
+        cannot be wrapped (bad extent, too short for GRE_L3, outer frame over
+        65535 bytes) has length 0 and its status in the row. Reads the total
+        back: one synchronisation of the stream.
+
+        The recipe, a tunnel endpoint as a match-action table: rule j of the
+        filter gets tunnel j.
+
+            rec = eng.parse(batch, out_kind=abi.OUT_RECORD)
+            idx, sel, rule = eng.select(batch, rec, flt, want_rule=True)
+            flows = eng.flow(sel, eng.gather_rows(rec, 64, idx))
+            outer, rows = eng.encap(sel, tunnels, rule, flows)
+        """
+        torch = _torch()
+        if align not in abi.GATHER_ALIGNS:
+            raise ValueError("align must be 1, 4, 8 or 16")
+        tc = tunnels.to_c()  # ValueError for what nexg_tunnels_check rejects
+        if tunnels.needs_flows and flows is None:
+            raise ValueError("a tunnel takes its source port from the flow hash: flows is needed")
+        dev = self.torch_device
+        n = batch.count
+        if index is not None and (index.dtype != torch.uint8 or index.device != dev or index.numel() < n):
+            raise ValueError(f"index: a uint8 tensor of {n} tunnel numbers on {dev} is needed")
+        if flows is not None and (flows.device != dev or flows.numel() * flows.element_size() < n * 8):
+            raise ValueError(f"flows: the {n} 8-byte rows of Engine.flow on {dev} are needed")
+        offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        ln = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if align != 1 else None
+        rows = torch.empty(max(n, 1) * 8, dtype=torch.uint8, device=dev) if report else None
+        ws_bytes = abi.encap_plan_workspace(n)
+        ws = self._workspace(ws_bytes)
+        fr = _frames(batch)
+        s = self._stream(stream)
+        self._check(self.lib.nexg_encap_plan(self.ctx, fr, ctypes.byref(tc), _ptr(index), align, _ptr(offs), _ptr(ln),
+                                             _ptr(ws), ws_bytes, s))
+        total = int(offs[n].item())  # waits for the kernels
+        data = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+        self._check(self.lib.nexg_encap_frames(self.ctx, fr, ctypes.byref(tc), _ptr(index), _ptr(flows), _ptr(offs),
+                                               _ptr(data), total, _ptr(rows), s))
+        out = FrameBatch(data=data[:total], count=n, offsets=offs, lengths=None if ln is None else ln[:n],
+                         hints=0 if ln is None else abi.FRAMES_MONOTONE)
+        return out, (rows[: n * 8] if report else None)
+
     def gather_rows(self, rows, row_bytes: int, index, stream=None):
         """Compact per-frame rows by a selected index (nexg_gather_rows):
         row k of the result is rows[index[k]], zeros where index[k] is past
