@@ -668,9 +668,9 @@ static inline uint64_t nexg_decap_select_workspace(uint64_t count) {
  *  5 pads     the bytes from the frame's end up to out_offsets[i + 1] are
  *             zero (fewer than 16 with the plan's offsets; at most 15 are
  *             written).
- * Out of scope: Geneve, NVGRE, the GRE checksum and routing, fragmentation to
- * an MTU, outer VLAN tags, an incrementing IPv4 id, fixing inner checksums;
- * nested encapsulation is the pass run twice. */
+ * Out of scope: Geneve, NVGRE, the GRE checksum and routing, outer VLAN tags,
+ * an incrementing IPv4 id, fixing inner checksums; nested encapsulation is the
+ * pass run twice, and fragmentation to an MTU the section below. */
 #define NEXG_ENCAP_VXLAN 1
 #define NEXG_ENCAP_GRE 2
 #define NEXG_ENCAP_UDP_CSUM  0x01u /* VXLAN: compute the outer UDP checksum (default: field 0) */
@@ -751,6 +751,128 @@ static inline uint64_t nexg_encap_plan_workspace(uint64_t count) {
 int nexg_encap_frames(nexg_ctx* ctx, const nexg_frames* frames, const nexg_tunnels* set, const uint8_t* tunnel_index,
                       const struct nexg_flow* flows, const uint64_t* out_offsets, uint8_t* out_data, uint64_t out_cap,
                       nexg_encapped* rows, void* stream);
+
+/* ---- IPv4 fragmentation to an MTU (RFC 791 section 3.2; extension) --------------
+ * What makes the output of the passes above fit a link: every IPv4 frame of a
+ * table whose total length exceeds `mtu` is cut into pieces that each carry the
+ * frame's Ethernet and IPv4 header, the bytes the reference's Ipv4PacketBuilder
+ * gives for each piece's fields (Ipv4Flags::{DontFragment, MoreFragments},
+ * fragment_offset, ipv4::checksum). The first one-to-many pass: a frame becomes
+ * 0..8183 output frames, so the plan scans twice (output frames, output bytes)
+ * and the fill writes a frame table with the input frame of each piece, the
+ * index nexg_gather_rows takes to carry per-frame rows (rule, tunnel, flow) to
+ * the pieces.
+ *
+ * Per frame i, in this order:
+ *  1 extent   An extent that leaves [0, data_bytes) or a length above 65535
+ *             (the gather's rule): 0 pieces, status NEXG_ERR_BAD_EXTENT, kind
+ *             NEXG_FRAG_NONE.
+ *  2 IPv6     bytes 12..13 are 0x86DD, len >= 54, version 6 and 40 +
+ *             payload_length <= len - 14: 0 pieces and kind NEXG_FRAG_TOO_BIG
+ *             when 40 + payload_length > mtu (routers never fragment IPv6),
+ *             else a pass-through.
+ *  3 not IPv4 bytes 12..13 are not 0x0800, len < 34, version != 4, IHL < 5,
+ *             14 + hl > len (hl = 4 IHL), total length TL < hl, or 14 + TL > len:
+ *             a pass-through, one output frame, the whole input frame copied
+ *             unchanged, kind NEXG_FRAG_PASS. VLAN-tagged frames fall here.
+ *  4 fits     TL <= mtu: a pass-through (the bytes past 14 + TL are copied too).
+ *  5 DF       the DF bit set and NEXG_FRAG_IGNORE_DF absent: 0 pieces, kind
+ *             NEXG_FRAG_TOO_BIG, status NEXG_FRAME_OK (the host builds the ICMP
+ *             "fragmentation required" message from the row).
+ *  6 split    D = TL - hl, p = (mtu - hl) & ~7, n = ceil(D / p); fo0 and MF0 are
+ *             the input's own fragment offset and MF bit (an input that is
+ *             already a fragment is split further). fo0 + (n - 1) p / 8 > 8191:
+ *             0 pieces, status NEXG_ERR_INVALID_LENGTH, kind NEXG_FRAG_NONE.
+ *             Otherwise kind NEXG_FRAG_SPLIT and piece k (0 <= k < n) is the 14
+ *             Ethernet bytes, the hl header bytes and data bytes [k p, k p + d_k)
+ *             of the input's IP payload, d_k = min(p, D - k p); its length is
+ *             14 + hl + d_k (input bytes past 14 + TL are dropped; no padding to
+ *             60 bytes). In the header: total length hl + d_k; identification,
+ *             TOS, TTL, protocol, addresses and the reserved flag bit unchanged;
+ *             DF unchanged, or cleared in every piece under IGNORE_DF; MF 1 for
+ *             k < n - 1 and MF0 for the last piece; fragment offset fo0 + k p / 8;
+ *             the checksum recomputed as ipv4::checksum over the piece's header.
+ *             Piece 0 keeps its options. In pieces k >= 1 the options are walked
+ *             from byte 20 to hl: type 0 stops the walk (the rest stays as it
+ *             is), type 1 advances one byte, otherwise L is the next byte, L < 2
+ *             or L above the bytes left stops the walk, a type with bit 7 (copied)
+ *             clear has all its L bytes set to 0x01, and the walk advances by L.
+ *             The header keeps its length, as Linux's forward path does.
+ *  7 pads     each output frame's start is rounded up to `align`; the pads are
+ *             zero.
+ * Out of scope: IPv6 fragment headers, reassembly, VLAN-tagged or tunnelled
+ * inner headers, padding to the Ethernet minimum, building the ICMP / ICMPv6
+ * error, a per-frame MTU, fixing L4 checksums (they do not change). */
+#define NEXG_FRAG_NONE 0     /* no output frame: an error status */
+#define NEXG_FRAG_PASS 1     /* one output frame, the input copied unchanged */
+#define NEXG_FRAG_SPLIT 2    /* `pieces` output frames */
+#define NEXG_FRAG_TOO_BIG 3  /* no output frame: over the MTU and not to be fragmented (DF, IPv6) */
+#define NEXG_FRAG_IGNORE_DF 0x1u
+typedef struct nexg_frag_option {  /* host memory, read during the call only */
+    uint32_t mtu;                  /* the largest IP total length, 68..65535 */
+    uint32_t flags;                /* NEXG_FRAG_* */
+    uint32_t align;                /* 1, 4, 8 or 16 */
+    uint32_t reserved;             /* must be 0 */
+} nexg_frag_option;
+typedef struct nexg_fragged {      /* 16 bytes, one per input frame */
+    uint8_t status;                /* NEXG_FRAME_OK / NEXG_ERR_* */
+    uint8_t kind;                  /* NEXG_FRAG_* */
+    uint8_t hdr_len;               /* hl of a split frame, else 0 */
+    uint8_t reserved;
+    uint16_t pieces;               /* output frames: 0, 1 or n */
+    uint16_t piece_data;           /* p of a split frame, else 0 */
+    uint32_t first;                /* index of its first output frame */
+    uint32_t reserved2;
+} nexg_fragged;
+
+/* Host only. NEXG_EINVAL: NULL, mtu outside 68..65535, unknown flag bits, an
+ * align other than 1, 4, 8 or 16, a nonzero reserved. */
+int nexg_frag_option_check(const nexg_frag_option* option);
+
+/* out_first[i] (count + 1 entries, 4-B aligned) = the number of output frames
+ * of the frames before i, out_bytes[i] (count + 1 entries, 8-B aligned) = the
+ * sum of their output frames' lengths, each rounded up to option->align; the
+ * totals are in the last entries. rows[i] (optional, 16-B aligned) reports
+ * frame i. workspace: caller-owned device memory (8-B aligned) of at least the
+ * bytes the helper below gives (NEXG_EINVAL when smaller): two u64 per 256-frame
+ * tile, turned into the tiles' exclusive scans in place. Scans only, no atomics.
+ * count == 0 writes the two zeros and launches nothing else. NEXG_EINVAL also
+ * for count > 2^32 - 1. The output frames are numbered with 32 bits; the call
+ * does not wait for the device, so it cannot return an error for a total that
+ * only the device knows: the total is summed in 64 bits, and out_first[count]
+ * == 2^32 - 1 says that it is 2^32 - 1 or more (a 65535-byte frame gives up to
+ * 8183 pieces, at mtu 68 and hl 60). The other prefixes then wrapped and are
+ * of no use: fragment a part of the table. (nexg_fragment_frames keeps its
+ * bounds whatever it is given.) Four kernels on `stream`. */
+int nexg_fragment_plan(nexg_ctx* ctx, const nexg_frames* frames, const nexg_frag_option* option, uint32_t* out_first,
+                       uint64_t* out_bytes, nexg_fragged* rows, void* workspace, uint64_t workspace_bytes, void* stream);
+static inline uint64_t nexg_fragment_plan_workspace(uint64_t count) {
+    const uint64_t tiles = (count + 255u) / 256u;
+    return 16u * ((tiles + 255u) / 256u * 256u) + 16u;
+}
+
+/* The output frames of frame i at out_data (16-B aligned) + out_bytes[i] on,
+ * each start rounded up to option->align and the pads zero, and for its k-th
+ * piece, f = out_first[i] + k: out_offsets[f] (out_count + 1 entries, 8-B
+ * aligned) = where it starts, out_len[f] its length, out_src[f] = i (4-B
+ * aligned, out_count entries each); out_offsets[out_count] = out_bytes[count].
+ * out_first and out_bytes are caller memory: whatever they hold, no byte store
+ * lands at or past out_cap or outside frame i's [out_bytes[i], out_bytes[i + 1]),
+ * no table store lands at an index at or above min(out_first[i + 1], out_count),
+ * and every loop is bounded by the shape recomputed from the frame's own bytes.
+ * Source reads follow the 16-B block rule and never leave a frame's blocks; the
+ * payload is read once. The output is never read. Deterministic, no atomics,
+ * no workspace. NEXG_EINVAL: an invalid option, a NULL out_first, out_bytes or
+ * out_offsets, a NULL out_len or out_src with out_count > 0, a NULL out_data
+ * with out_cap > 0, a misaligned pointer, count or out_count > 2^32 - 1.
+ * count == 0 launches nothing but the copy of the total. With align 1,
+ * {out_data, total, out_offsets} is a packed batch that nexg_parse_batch,
+ * nexg_encap_plan, nexg_rewrite_batch and nexg_tx_send_batch take as it
+ * stands; with a larger align, {out_data, total, out_offsets, out_len} an
+ * offsets + lengths batch (monotone). One kernel on `stream`. */
+int nexg_fragment_frames(nexg_ctx* ctx, const nexg_frames* frames, const nexg_frag_option* option,
+                         const uint32_t* out_first, const uint64_t* out_bytes, uint64_t out_count, uint64_t* out_offsets,
+                         uint32_t* out_len, uint32_t* out_src, uint8_t* out_data, uint64_t out_cap, void* stream);
 
 /* ---- DNS messages ------------------------------------------------------------
  * Frame::try_from_buf stops at the UDP header; the reference's DNS parser

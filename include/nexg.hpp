@@ -42,6 +42,10 @@
  *                           GrePacket::to_bytes (gre.rs:115-160) inside the
  *                           Ethernet / IP / UDP builders, around every frame
  *                           of a batch, one tunnel per filter rule
+ *   FragOption, Engine::fragment_plan / fragment / fragment_bufs
+ *                           RFC 791 fragmentation to an MTU: each piece the
+ *                           bytes Ipv4PacketBuilder gives for its fields
+ *                           (Ipv4Flags, fragment_offset, ipv4::checksum)
  *   FlowOption, Engine::flow / flow_partition / flow_bufs
  *                           no reference counterpart (an extension): the
  *                           Toeplitz RSS hash of every frame's flow key and the
@@ -1263,6 +1267,34 @@ class TunnelSet {
     }
 };
 
+/* ---- IPv4 fragmentation to an MTU ------------------------------------------------ */
+
+// Builder of a nexg_frag_option. get() throws nexg::Error where
+// nexg_fragment_plan would return NEXG_EINVAL.
+//   FragOption(1500).ignore_df().align(16)
+class FragOption {
+   public:
+    nexg_frag_option o{};
+
+    explicit FragOption(uint32_t mtu) {
+        o.mtu = mtu;
+        o.align = 1;
+    }
+    FragOption& ignore_df(bool on = true) {
+        o.flags = on ? (o.flags | NEXG_FRAG_IGNORE_DF) : (o.flags & ~NEXG_FRAG_IGNORE_DF);
+        return *this;
+    }
+    FragOption& align(uint32_t a) {
+        o.align = a;
+        return *this;
+    }
+    // the option, checked as nexg_fragment_plan checks it
+    const nexg_frag_option& get() const {
+        if (nexg_frag_option_check(&o) != NEXG_OK) throw Error("FragOption: not a valid nexg_frag_option (include/nexg.h)");
+        return o;
+    }
+};
+
 /* ---- the engine --------------------------------------------------------- */
 
 // The calling thread's current device switched for a scope and restored after
@@ -2250,6 +2282,87 @@ class Engine {  // one nexg context on one gfx950 device, one stream
         check_hip(hipMemcpyAsync(out.offsets.data(), d_off, (n + 1) * 8, hipMemcpyDeviceToHost, stream_), "D2H");
         check_hip(hipMemcpyAsync(out.lengths.data(), d_len, n * 4, hipMemcpyDeviceToHost, stream_), "D2H");
         if (total) check_hip(hipMemcpyAsync(out.data.data(), d_data, total, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        return out;
+    }
+
+    // What fragment will write (nexg_fragment_plan): out_first and out_bytes
+    // hold frames.count + 1 entries, rows (may be null) frames.count. Returns
+    // the number of output frames and their bytes (one stream
+    // synchronisation) to allocate for fragment; throws when the output
+    // frames do not fit their 32-bit numbers.
+    struct FragmentTotals {
+        uint64_t frames, bytes;
+    };
+    FragmentTotals fragment_plan(const nexg_frames& frames, const FragOption& option, uint32_t* out_first,
+                                 uint64_t* out_bytes, nexg_fragged* rows = nullptr) {
+        DeviceScope ds(device_);
+        const uint64_t wsb = nexg_fragment_plan_workspace(frames.count);
+        void* ws = scratch(54, wsb);
+        check(nexg_fragment_plan(ctx_, &frames, &option.get(), out_first, out_bytes, rows, ws, wsb, stream_),
+              "nexg_fragment_plan");
+        uint32_t n = 0;
+        FragmentTotals t{0, 0};
+        check_hip(hipMemcpyAsync(&n, out_first + frames.count, 4, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipMemcpyAsync(&t.bytes, out_bytes + frames.count, 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        if (n == 0xFFFFFFFFu) throw Error("fragment_plan: 2^32 - 1 output frames or more (include/nexg.h)");
+        t.frames = n;
+        return t;
+    }
+
+    // Every IPv4 frame over the MTU as its RFC 791 fragments, every other
+    // frame unchanged, at out_data + out_bytes[i] on, pads zero, nothing at or
+    // past out_cap (nexg_fragment_frames); out_offsets (out_count + 1
+    // entries), out_len and out_src (out_count each) are the output frames'
+    // table and the input frame of each.
+    void fragment(const nexg_frames& frames, const FragOption& option, const uint32_t* out_first, const uint64_t* out_bytes,
+                  uint64_t out_count, uint64_t* out_offsets, uint32_t* out_len, uint32_t* out_src, uint8_t* out_data,
+                  uint64_t out_cap) {
+        DeviceScope ds(device_);
+        check(nexg_fragment_frames(ctx_, &frames, &option.get(), out_first, out_bytes, out_count, out_offsets, out_len,
+                                   out_src, out_data, out_cap, stream_),
+              "nexg_fragment_frames");
+    }
+
+    // fragment of host frames: output frame f lies in `data` at offsets[f],
+    // lengths[f] bytes, and came from input frame src[f]; rows has one entry
+    // per input frame.
+    struct Fragged {
+        std::vector<nexg_fragged> rows;
+        std::vector<uint64_t> offsets;  // lengths.size() + 1
+        std::vector<uint32_t> lengths, src;
+        std::vector<uint8_t> data;
+    };
+    Fragged fragment_bufs(const std::vector<std::vector<uint8_t>>& frames, const FragOption& option) {
+        DeviceScope ds(device_);
+        const uint64_t n = frames.size();
+        Fragged out;
+        out.offsets.assign(1, 0);
+        (void)option.get();
+        if (n == 0) return out;
+        HostBatch hb(*this, frames);
+        uint32_t* d_first = static_cast<uint32_t*>(scratch(55, (n + 1) * 4));
+        uint64_t* d_bytes = static_cast<uint64_t*>(scratch(56, (n + 1) * 8));
+        nexg_fragged* d_rows = static_cast<nexg_fragged*>(scratch(57, n * sizeof(nexg_fragged)));
+        const FragmentTotals t = fragment_plan(hb.fb, option, d_first, d_bytes, d_rows);
+        uint64_t* d_off = static_cast<uint64_t*>(scratch(58, (t.frames + 1) * 8));
+        uint32_t* d_len = static_cast<uint32_t*>(scratch(59, t.frames * 4));
+        uint32_t* d_src = static_cast<uint32_t*>(scratch(60, t.frames * 4));
+        uint8_t* d_data = static_cast<uint8_t*>(scratch(61, t.bytes));
+        fragment(hb.fb, option, d_first, d_bytes, t.frames, d_off, d_len, d_src, d_data, t.bytes);
+        out.rows.resize(n);
+        out.offsets.resize(t.frames + 1);
+        out.lengths.resize(t.frames);
+        out.src.resize(t.frames);
+        out.data.resize(t.bytes);
+        check_hip(hipMemcpyAsync(out.rows.data(), d_rows, n * sizeof(nexg_fragged), hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipMemcpyAsync(out.offsets.data(), d_off, (t.frames + 1) * 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        if (t.frames) {
+            check_hip(hipMemcpyAsync(out.lengths.data(), d_len, t.frames * 4, hipMemcpyDeviceToHost, stream_), "D2H");
+            check_hip(hipMemcpyAsync(out.src.data(), d_src, t.frames * 4, hipMemcpyDeviceToHost, stream_), "D2H");
+        }
+        if (t.bytes) check_hip(hipMemcpyAsync(out.data.data(), d_data, t.bytes, hipMemcpyDeviceToHost, stream_), "D2H");
         check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
         return out;
     }

@@ -68,6 +68,10 @@ def load():
         "nexg_tunnels_check": (I, [ctypes.POINTER(abi.TunnelsC)]),
         "nexg_encap_plan": (I, [P, ctypes.POINTER(abi.Frames), ctypes.POINTER(abi.TunnelsC), P, U32, P, P, P, U64, P]),
         "nexg_encap_frames": (I, [P, ctypes.POINTER(abi.Frames), ctypes.POINTER(abi.TunnelsC), P, P, P, P, U64, P, P]),
+        "nexg_frag_option_check": (I, [ctypes.POINTER(abi.FragOptionC)]),
+        "nexg_fragment_plan": (I, [P, ctypes.POINTER(abi.Frames), ctypes.POINTER(abi.FragOptionC), P, P, P, P, U64, P]),
+        "nexg_fragment_frames": (I, [P, ctypes.POINTER(abi.Frames), ctypes.POINTER(abi.FragOptionC), P, P, U64, P, P, P, P,
+                                     U64, P]),
         "nexg_flow_batch": (I, [P, ctypes.POINTER(abi.Frames), P, ctypes.POINTER(abi.FlowOptionC), P, P]),
         "nexg_flow_partition": (I, [P, ctypes.POINTER(abi.Frames), P, U32, P, P, P, P, P, U64, P]),
         "nexg_flow_sort": (I, [P, P, U64, P, P, U64, P]),

@@ -450,6 +450,31 @@ def encap_plan_workspace(count):
     return gather_plan_workspace(count)
 
 
+# IPv4 fragmentation to an MTU (nexg_fragment_plan / nexg_fragment_frames; an
+# extension: the reference has the fields, not the procedure)
+FRAG_NONE, FRAG_PASS, FRAG_SPLIT, FRAG_TOO_BIG = 0, 1, 2, 3
+FRAG_IGNORE_DF = 0x1
+FRAG_MTU_MIN, FRAG_MTU_MAX = 68, 65535
+FRAGGED_DTYPE = np.dtype([("status", "u1"), ("kind", "u1"), ("hdr_len", "u1"), ("reserved", "u1"), ("pieces", "<u2"),
+                          ("piece_data", "<u2"), ("first", "<u4"), ("reserved2", "<u4")])
+assert FRAGGED_DTYPE.itemsize == 16
+
+
+class FragOptionC(ctypes.Structure):
+    """struct nexg_frag_option"""
+    _fields_ = [("mtu", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("align", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+def fragment_plan_workspace(count):
+    """nexg_fragment_plan_workspace: bytes of nexg_fragment_plan's workspace."""
+    tiles = (int(count) + 255) // 256
+    return 16 * ((tiles + 255) // 256 * 256) + 16
+
+
+FRAG_TOTAL_OVERFLOW = 0xFFFFFFFF  # out_first[count] of nexg_fragment_plan: 2^32 - 1 output frames or more
+
+
 # DNS messages (nexg_dns_batch / nexg_dns_entries)
 DNS_ANY_UDP = 0x1
 DNS_PORT = 53  # what nexg_dns_option.port = 0 means
@@ -640,7 +665,7 @@ def flow_table_workspace(n_in, n_groups):
 HEADER_INLINE = ("nexg_sparse_decode", "nexg_grouped_code", "nexg_grouped_exc_slot", "nexg_offsets32_bases",
                  "nexg_offsets32_bytes", "nexg_decap_select_workspace", "nexg_dns_tile_first_bytes",
                  "nexg_select_workspace", "nexg_match_select_workspace", "nexg_gather_plan_workspace", "nexg_encap_plan_workspace",
-                 "nexg_flow_partition_workspace",
+                 "nexg_fragment_plan_workspace", "nexg_flow_partition_workspace",
                  "nexg_flow_sort_workspace", "nexg_flow_groups_workspace", "nexg_flow_table_workspace")
 
 #: every symbol include/nexg.h declares (tests check the .so exports them)
@@ -652,6 +677,7 @@ EXPORTED_SYMBOLS = (
     "nexg_patterns_check", "nexg_match_batch", "nexg_match_select",
     "nexg_actions_check", "nexg_rewrite_batch",
     "nexg_tunnels_check", "nexg_encap_plan", "nexg_encap_frames",
+    "nexg_frag_option_check", "nexg_fragment_plan", "nexg_fragment_frames",
     "nexg_flow_batch", "nexg_flow_partition", "nexg_flow_sort", "nexg_flow_groups",
     "nexg_flow_table_merge",
     "nexg_probe_span_clock", "nexg_probe_latency",

@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include "encap_core.hpp"
+#include "fragment_core.hpp"
 #include "match_core.hpp"
 #include "nexg_internal.hpp"
 #include "rewrite_core.hpp"
@@ -533,6 +534,46 @@ int nexg_encap_frames(nexg_ctx* ctx, const nexg_frames* frames, const nexg_tunne
     DeviceGuard g(ctx);
     return launched(ctx, nexg::launch_encap_frames(a, es, tunnel_index, flows, out_offsets, out_data, out_cap, rows,
                                                    as_stream(stream)));
+}
+
+int nexg_frag_option_check(const nexg_frag_option* option) { return nexg::check_frag_option(option) ? NEXG_EINVAL : NEXG_OK; }
+
+int nexg_fragment_plan(nexg_ctx* ctx, const nexg_frames* frames, const nexg_frag_option* option, uint32_t* out_first,
+                       uint64_t* out_bytes, nexg_fragged* rows, void* workspace, uint64_t workspace_bytes, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    if (const char* why = nexg::check_frag_option(option)) return fail(ctx, NEXG_EINVAL, "fragment_plan: %s", why);
+    const uint64_t count = frames->count;
+    if (int rc = check_count(ctx, "fragment_plan", count)) return rc;
+    if (!out_first || !out_bytes) return fail(ctx, NEXG_EINVAL, "NULL out_first or out_bytes%s", nullptr);
+    if (count && !workspace) return fail(ctx, NEXG_EINVAL, "NULL workspace%s", nullptr);
+    if (int rc = check_workspace(ctx, "fragment_plan", count, workspace_bytes, nexg_fragment_plan_workspace(count))) return rc;
+    if (misaligned(7u, out_bytes, workspace) || misaligned(3u, out_first) || misaligned(15u, rows))
+        return fail(ctx, NEXG_EINVAL, "misaligned output, rows or workspace%s", nullptr);
+    const nexg::ParseArgs a = to_args(frames);
+    DeviceGuard g(ctx);
+    return launched(ctx, nexg::launch_fragment_plan(a, option->mtu, option->flags, option->align, out_first, out_bytes, rows,
+                                                    workspace, as_stream(stream)));
+}
+
+int nexg_fragment_frames(nexg_ctx* ctx, const nexg_frames* frames, const nexg_frag_option* option,
+                         const uint32_t* out_first, const uint64_t* out_bytes, uint64_t out_count, uint64_t* out_offsets,
+                         uint32_t* out_len, uint32_t* out_src, uint8_t* out_data, uint64_t out_cap, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    if (const char* why = nexg::check_frag_option(option)) return fail(ctx, NEXG_EINVAL, "fragment_frames: %s", why);
+    if (int rc = check_count(ctx, "fragment_frames", frames->count)) return rc;
+    if (out_count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "fragment_frames: more than 2^32 - 1 output frames%s", nullptr);
+    if (!out_first || !out_bytes || !out_offsets) return fail(ctx, NEXG_EINVAL, "NULL out_first, out_bytes or out_offsets%s", nullptr);
+    if (out_count && (!out_len || !out_src)) return fail(ctx, NEXG_EINVAL, "NULL out_len or out_src%s", nullptr);
+    if (out_cap && !out_data) return fail(ctx, NEXG_EINVAL, "NULL out_data with a nonzero capacity%s", nullptr);
+    if (misaligned(7u, out_bytes, out_offsets) || misaligned(3u, out_first, out_len, out_src) || misaligned(15u, out_data))
+        return fail(ctx, NEXG_EINVAL, "misaligned out_first, out_bytes, table or out_data%s", nullptr);
+    const nexg::ParseArgs a = to_args(frames);
+    DeviceGuard g(ctx);
+    return launched(ctx, nexg::launch_fragment_frames(a, option->mtu, option->flags, option->align, out_first, out_bytes,
+                                                      out_count, out_offsets, out_len, out_src, out_data, out_cap,
+                                                      as_stream(stream)));
 }
 
 int nexg_gather_rows(nexg_ctx* ctx, const void* rows, uint32_t row_bytes, uint64_t rows_count,

@@ -125,6 +125,16 @@ hipError_t launch_encap_frames(const ParseArgs& a, const EncapSet& set, const ui
                                const uint64_t* out_offsets, uint8_t* out_data, uint64_t out_cap, nexg_encapped* rows,
                                hipStream_t s);
 
+// nexg_fragment_plan / nexg_fragment_frames (nexg_fragment.hip); the option has
+// passed check_frag_option (fragment_core.hpp). workspace: as
+// nexg_fragment_plan_workspace sizes it (workspace_layout.hpp FragPlanLayout),
+// left holding the tiles' exclusive scans.
+hipError_t launch_fragment_plan(const ParseArgs& a, uint32_t mtu, uint32_t flags, uint32_t align, uint32_t* out_first,
+                                uint64_t* out_bytes, nexg_fragged* rows, void* workspace, hipStream_t s);
+hipError_t launch_fragment_frames(const ParseArgs& a, uint32_t mtu, uint32_t flags, uint32_t align, const uint32_t* out_first,
+                                  const uint64_t* out_bytes, uint64_t out_count, uint64_t* out_offsets, uint32_t* out_len,
+                                  uint32_t* out_src, uint8_t* out_data, uint64_t out_cap, hipStream_t s);
+
 // nexg_dns_batch / nexg_dns_entries (nexg_dns.hip). tile_first: one u64 per
 // 256-frame tile + 1, left holding the tiles' exclusive scan and the total.
 hipError_t launch_dns(const ParseArgs& a, const nexg_record* recs, uint32_t any_udp, uint32_t port, nexg_dns* out,

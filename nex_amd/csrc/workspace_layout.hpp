@@ -35,6 +35,27 @@ struct MatchSelectLayout {
     }
 };
 
+// nexg_fragment_plan_workspace: two u64 per 256-frame tile, each table rounded
+// up to whole scan steps of 256 tiles, then the output frames' total in the
+// first 8 of the 16 spare bytes
+struct FragPlanLayout {
+    uint64_t tiles;
+    uint64_t tile_frames;   // u64[tiles]
+    uint64_t tile_bytes;    // u64[tiles]
+    uint64_t frames_total;  // u64[1]
+    uint64_t bytes;
+    static FragPlanLayout from(uint64_t count) {
+        FragPlanLayout w;
+        w.tiles = (count + 255u) / 256u;
+        const uint64_t table = 8u * ((w.tiles + 255u) / 256u * 256u);
+        w.tile_frames = 0;
+        w.tile_bytes = table;
+        w.frames_total = 2u * table;
+        w.bytes = 2u * table + 16u;
+        return w;
+    }
+};
+
 // nexg_flow_partition_workspace: the scan's total, one u32 per chunk of 1024
 // counters (an even number of slots, so the counters start on 8 B), then the
 // buckets x tiles counters, bucket-major

@@ -560,6 +560,59 @@ class Engine:
                          hints=0 if ln is None else abi.FRAMES_MONOTONE)
         return out, (rows[: n * 8] if report else None)
 
+    def fragment(self, batch: FrameBatch, mtu: int, ignore_df: bool = False, align: int = 1, report=True, stream=None):
+        """Every IPv4 frame of `batch` whose total length exceeds `mtu` (68 to
+        65535) cut into RFC 791 fragments, every other frame copied unchanged
+        (nexg_fragment_plan + nexg_fragment_frames; the rule is in
+        include/nexg.h, restated by nex_amd.fragment.fragment_host). A frame
+        with DF set that does not fit gives no output frame unless
+        `ignore_df`, which clears DF in the pieces; nor does an IPv6 frame
+        over the MTU, a bad extent or a fragment offset that would overflow:
+        the row says which. Returns (FrameBatch, src_index, rows): the batch
+        owns its data, packed (offsets only) with align 1, offsets + lengths
+        with each output frame's start rounded up to `align` (4, 8 or 16) and
+        the pads zero; src_index is an int32 device tensor (bit patterns of
+        u32) with the input frame of each output frame, which
+        Engine.gather_rows takes as it stands; rows is the
+        nexg_fragged[count] report (uint8 device tensor, abi.FRAGGED_DTYPE)
+        or None. Reads the two totals back: one synchronisation of the
+        stream. ValueError when the output frames would number 2^32 - 1 or
+        more (they are numbered with 32 bits).
+
+        The recipe, a tunnel endpoint whose link has a 1500-byte MTU:
+
+            outer, _ = eng.encap(sel, tunnels, rule, flows)
+            pieces, src, rows = eng.fragment(outer, 1500)
+            rule_of_piece = eng.gather_rows(rule_rows, 4, src)
+        """
+        torch = _torch()
+        from .fragment import FragOption
+        oc = FragOption(int(mtu), abi.FRAG_IGNORE_DF if ignore_df else 0, align).to_c()  # ValueError as the C check
+        dev = self.torch_device
+        n = batch.count
+        first = torch.empty(n + 1, dtype=torch.int32, device=dev)
+        nbytes = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        rows = torch.empty(max(n, 1) * 16, dtype=torch.uint8, device=dev) if report else None
+        ws_bytes = abi.fragment_plan_workspace(n)
+        ws = self._workspace(ws_bytes)
+        fr = _frames(batch)
+        s = self._stream(stream)
+        self._check(self.lib.nexg_fragment_plan(self.ctx, fr, ctypes.byref(oc), _ptr(first), _ptr(nbytes), _ptr(rows),
+                                                _ptr(ws), ws_bytes, s))
+        totals = torch.stack((first[n].to(torch.int64) & 0xFFFFFFFF, nbytes[n])).cpu()  # waits for the kernels
+        k, total = int(totals[0]), int(totals[1])
+        if k == abi.FRAG_TOTAL_OVERFLOW:
+            raise ValueError("2^32 - 1 output frames or more: fragment a part of the batch")
+        offs = torch.empty(k + 1, dtype=torch.int64, device=dev)
+        ln = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
+        src = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
+        data = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+        self._check(self.lib.nexg_fragment_frames(self.ctx, fr, ctypes.byref(oc), _ptr(first), _ptr(nbytes), k, _ptr(offs),
+                                                  _ptr(ln), _ptr(src), _ptr(data), total, s))
+        out = FrameBatch(data=data[:total], count=k, offsets=offs, lengths=None if align == 1 else ln[:k],
+                         hints=0 if align == 1 else abi.FRAMES_MONOTONE)
+        return out, src[:k], (rows[: n * 16] if report else None)
+
     def gather_rows(self, rows, row_bytes: int, index, stream=None):
         """Compact per-frame rows by a selected index (nexg_gather_rows):
         row k of the result is rows[index[k]], zeros where index[k] is past
