@@ -478,7 +478,7 @@ hipError_t launch_lane(ProbeArgs& a, const uint8_t* tmpl, int fam, int kind, hip
     } while (0)
     if (kind == kL4Icmp && fam == 4 && p48) hipLaunchKernelGGL((k_build_lane<4, kL4Icmp, 48, 44>), g, b, lds, s, a);
     else if (kind == kL4Icmp && fam == 4) NEXG_LANE(4, kL4Icmp);
-    else if (kind == kL4Icmp) NEXG_LANE(6, kL4Icmp);
+    else if (kind == kL4Icmp) return hipErrorInvalidValue;  // ICMPv6: try_probe_l4 never sends it here, no instance
     else if (fam == 4) NEXG_LANE(4, kL4Tcp);
     else NEXG_LANE(6, kL4Tcp);
 #undef NEXG_LANE

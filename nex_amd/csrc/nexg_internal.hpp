@@ -29,11 +29,12 @@ struct ParseArgs {
     const uint64_t* off_bases = nullptr;  // NEXG_FRAMES_OFFSETS32 over 4 GiB: one full offset per 256 frames
 };
 
-// Kernel variants of the parse path.
+// Kernel variants of the parse path, as choose_parse_variant
+// returns them. (NEXG_OUT_SLICE stages any other layout in a per-lane 128-B
+// window, k_parse<1, ...>: launch_slice picks it, no variant names it.)
 enum class ParseVariant {
     TileStride64,   // fixed 64-B stride: coalesced tile staging into LDS
     TileStride,     // fixed stride (multiple of 16, <= 128): tile staging
-    LaneWindow,     // any layout: per-lane 128-B window, lane sums its own tail
     TwoPass,        // any layout: k_tail_sums (bytes past 80) + k_parse_lane80
     SpanTile,       // packed layouts: 16-KiB sub-tiles through LDS + chunk prefix sums
 };

@@ -126,9 +126,6 @@ static hipError_t launch_parse_out(ParseVariant v, const ParseArgs& a, hipStream
         case ParseVariant::TileStride:
             hipLaunchKernelGGL((k_parse<0, OUT, 0, 128>), grid, block, 0, s, a);
             break;
-        case ParseVariant::LaneWindow:
-            hipLaunchKernelGGL((k_parse<1, OUT, 0, 128>), grid, block, 0, s, a);
-            break;
         case ParseVariant::SpanTile:
             // 24-KiB sub-tiles at 5 waves/SIMD (31 KB LDS, 5 workgroups per CU:
             // 120 KB in flight per CU): in one process +0.9 % over 20 KiB at 6
@@ -139,13 +136,13 @@ static hipError_t launch_parse_out(ParseVariant v, const ParseArgs& a, hipStream
             // over 16 KiB and 24 KiB equal, 28-32 KiB slower:
             // profiles/r02_kbench/kbench_subtile.log). Records (about 100
             // VGPRs) run uncapped on 16 KiB: capping them spills 44+ B.
-            // (Two-barrier / double-buffered generations measured slower,
-            // 0.66-0.69 vs 0.75: tools/kbench.hip keeps them for A/B.)
-            if (OUT == NEXG_OUT_RECORD) hipLaunchKernelGGL((k_parse_span<OUT, 1, 16384, 1>), grid, block, 0, s, a);
-            else if (OUT == NEXG_OUT_GROUPED)
-                hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 1, NEXG_SPAN_SUB, NEXG_SPAN_WPE>), grid, block, 0, s,
+            // if constexpr: each OUT compiles the one instance it launches
+            if constexpr (OUT == NEXG_OUT_RECORD)
+                hipLaunchKernelGGL((k_parse_span<OUT, 16384, 1>), grid, block, 0, s, a);
+            else if constexpr (OUT == NEXG_OUT_GROUPED)
+                hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, NEXG_SPAN_SUB, NEXG_SPAN_WPE>), grid, block, 0, s,
                                    grouped_as_sparse(a));
-            else hipLaunchKernelGGL((k_parse_span<OUT, 1, NEXG_SPAN_SUB, NEXG_SPAN_WPE>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((k_parse_span<OUT, NEXG_SPAN_SUB, NEXG_SPAN_WPE>), grid, block, 0, s, a);
             break;
         case ParseVariant::TwoPass:
             hipLaunchKernelGGL((k_tail_sums<OUT, 4>), grid, block, 0, s, a);
@@ -173,7 +170,7 @@ static hipError_t launch_slice(ParseVariant v, const ParseArgs& a, hipStream_t s
 hipError_t launch_span_clock(const ParseArgs& a, hipStream_t s) {
     if (a.count == 0) return hipSuccess;
     const uint64_t blocks = (a.count + kTile - 1) / kTile;
-    hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 1, NEXG_SPAN_SUB, NEXG_SPAN_WPE, true>), dim3((uint32_t)blocks),
+    hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, NEXG_SPAN_SUB, NEXG_SPAN_WPE, true>), dim3((uint32_t)blocks),
                        dim3(kTile), 0, s, grouped_as_sparse(a));
     return hipGetLastError();
 }

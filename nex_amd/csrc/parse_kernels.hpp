@@ -11,16 +11,14 @@ namespace nexg {
 
 constexpr uint32_t kTile = 256;
 
-// NEXG_OUT_DESC store shape of the span kernel and the lane-per-frame
-// kernels (A/B builds): 2 = a span tile's descriptors staged in LDS and stored
-// as 16-B non-temporal pairs, 8-B non-temporal per lane elsewhere; 1 = 8-B
-// non-temporal per lane; 0 = 8-B plain per lane. In one process (profiles/
-// r05/desc_ab/): 16M IMIX 0.751 / 0.749 / 0.736 of 8 TB/s. The fixed-stride
-// tile kernel (k_parse MODE 0) stores plain 8-B descriptors per lane: UDP64
-// 0.725 plain against 0.718 non-temporal and 0.703 staged.
-#ifndef NEXG_DESC_MODE
-#define NEXG_DESC_MODE 2
-#endif
+// NEXG_OUT_DESC store shapes: a span tile's descriptors are staged in LDS and
+// stored as 16-B non-temporal pairs, the lane-per-frame kernels store 8 B
+// non-temporal per lane. In one process (profiles/r05/desc_ab/), 16M IMIX:
+// 0.751 of 8 TB/s, against 0.749 with 8-B non-temporal and 0.736 with 8-B
+// plain stores per lane in the span kernel too. The fixed-stride tile kernel
+// (k_parse MODE 0) stores plain 8-B descriptors per lane: UDP64 0.725 plain
+// against 0.718 non-temporal and 0.703 staged.
+
 // k_parse_span: bytes of the previous sub-tile kept in front (and of pad
 // behind): at least the slot, so a head window that starts there is whole
 constexpr uint32_t kApron = NEXG_SPAN_SLOT > 96 ? NEXG_SPAN_SLOT : 96;
@@ -59,8 +57,7 @@ __device__ __forceinline__ void store_result(void* out, uint64_t idx, const nexg
     } else if (OUT == NEXG_OUT_DESC) {  // non-temporal, as the flags / verdict streams
         typedef uint32_t v2u __attribute__((ext_vector_type(2)));
         const v2u d{r.flags, (uint32_t)r.payload_off | ((uint32_t)r.payload_len << 16)};
-        if (NEXG_DESC_MODE >= 1) __builtin_nontemporal_store(d, reinterpret_cast<v2u*>(out) + idx);
-        else reinterpret_cast<v2u*>(out)[idx] = d;
+        __builtin_nontemporal_store(d, reinterpret_cast<v2u*>(out) + idx);
     } else {
         uint4 v[4];
         __builtin_memcpy(v, &r, sizeof(r));
@@ -296,7 +293,7 @@ __global__ __launch_bounds__(256) void k_parse(ParseArgs a) {
     }
     // MODE 0 + RECORD / DESC: every thread stays for the coalesced copy-out
     constexpr bool kStaged = MODE == 0 && OUT == NEXG_OUT_RECORD && PITCH >= 64;
-    constexpr bool kPlainDesc = MODE == 0 && OUT == NEXG_OUT_DESC;  // see NEXG_DESC_MODE
+    constexpr bool kPlainDesc = MODE == 0 && OUT == NEXG_OUT_DESC;  // plain 8-B stores: the NEXG_OUT_DESC note at the top
     if constexpr (OUT == NEXG_OUT_SLICE) {  // FrameSlice boundaries from the same staging
         if (tid < nf) {
             nexg_slice sl;
@@ -583,10 +580,6 @@ __global__ __launch_bounds__(256) void k_parse_lane80(ParseArgs a) {
     store_out<OUT>(a, idx, valid, r);
 }
 
-}  // namespace nexg
-
-namespace nexg {
-
 // ---- packed-span path (offset tables without a lengths array, any stride) ----
 //
 // A workgroup owns 256 consecutive frames (one per thread). Packed frames are
@@ -670,30 +663,33 @@ __device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v) {
 #define NEXG_SPAN_RTSTAMP(k) \
     do { if constexpr (TIMING) { if (t == 0) a.stamps[blockIdx.x * 8ull + (k)] = __builtin_amdgcn_s_memrealtime(); } } while (0)
 
-// NB = 2: sub-tile k stages into buffer k&1, so the barrier that publishes
-// sub-tile k also retires every lookup into sub-tile k-2's buffer (3 barriers
-// per sub-tile, ~42 KB LDS); NB = 1 (the library's): one buffer and a 4th
-// barrier (~25 KB LDS, 6 workgroups per CU).
-#ifndef NEXG_SPAN_NT
-#define NEXG_SPAN_NT true  // sub-tile fetch cache policy (A/B builds override)
-#endif
-#ifndef NEXG_SPAN_PF
-#define NEXG_SPAN_PF 0  // offset-table prefetch distance in same-XCD dispatches (A/B builds)
-#endif
-#ifndef NEXG_SPAN_DEPTH
-#define NEXG_SPAN_DEPTH 1  // sub-tiles in flight beside the one being scanned (A/B builds: 2)
-#endif
-template <int OUT, int NB = 1, uint32_t SUB = 16384, int WPE = 1, bool TIMING = false>
+// One stage buffer, one sub-tile in flight in registers while the staged one
+// is scanned, non-temporal fetches, four barriers per sub-tile: stage | wave
+// sums | prefixes | lookups done, so the next sub-tile may overwrite the
+// buffer (~25 KB of LDS at SUB = 16 KiB). SUB and WPE (waves per SIMD, the
+// VGPR cap) are the library's NEXG_SPAN_SUB / NEXG_SPAN_WPE, see
+// launch_parse_out. Measured and rejected, the code last in commit 25e0fad
+// ('Span kernel', 'Tuning history', round 6 'Span kernel
+// variants measured and not taken'): a second stage buffer that saves the
+// fourth barrier (~42 KB of LDS, 3 workgroups per CU: 4.6 against 5.9 TB/s;
+// with the two-barrier scan 0.66-0.69 against 0.75 of 8 TB/s), two sub-tiles
+// in flight over two register sets (4 waves: IMIX 0.865, real 0.785, mix
+// 0.723 against 0.851 / 0.784 / 0.786), an L2 warm-up of a later group's
+// offset table (IMIX +0.2 %, mix -0.6 %).
+template <int OUT, uint32_t SUB = 16384, int WPE = 1, bool TIMING = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void k_parse_span(ParseArgs a) {
-    // each stage buffer: [96-B apron | SUB bytes | 96-B pad]; the apron holds
+    // the stage buffer: [96-B apron | SUB bytes | 96-B pad]; the apron holds
     // the previous sub-tile's last 96 bytes, so a head window that starts
     // there is read in the sub-tile where it ends (one gather, no straddle)
     // (after the loop the bytes become per-lane 80-B SpanFrame / record slots)
     constexpr uint32_t kStage = kApron + SUB + kApron > kTile * SpanFrame::kSlot ? kApron + SUB + kApron
                                                                                  : kTile * SpanFrame::kSlot;
-    __shared__ __attribute__((aligned(16))) uint8_t s_bytes[NB][kStage];
-    __shared__ __attribute__((aligned(16))) uint32_t s_pfx[NB][(SUB / 16u) + 4];  // [1024] = total
-    __shared__ uint32_t s_wsum[NB][4];
+    // (declared [1][kStage]: as a plain uint8_t[kStage] the record instance
+    // compiles to other code, 4 instructions shorter, which nobody has timed)
+    __shared__ __attribute__((aligned(16))) uint8_t s_stage[1][kStage];
+    uint8_t* const s_bytes = s_stage[0];
+    __shared__ __attribute__((aligned(16))) uint32_t s_pfx[(SUB / 16u) + 4];  // [1024] = total
+    __shared__ uint32_t s_wsum[4];
     __shared__ uint64_t s_span[2];
     __shared__ uint32_t s_hist[2 * kBuckets + 1];  // generic-pass bucket counts, bases, total
     const uint32_t t = threadIdx.x, lane = t & 63u, wv = t >> 6;
@@ -715,17 +711,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     // profiles/r05/grouped_as_sparse/)
     if (OUT == NEXG_OUT_SPARSE && a.grouped_heads && lane == 0 && have) a.grouped_heads[idx >> 6] = NEXG_GROUPED_TILE_RUN;
     if (OUT == NEXG_OUT_GROUPED && lane == 0 && have) reinterpret_cast<uint8_t*>(a.out)[idx >> 6] = 0;
-#if NEXG_SPAN_PF
-    // warm this XCD's L2 with the offset table of the group its workgroup
-    // NEXG_SPAN_PF dispatches later will take (same XCD: block + 8 k): one
-    // u64 per 64-B line of that group's 2 KiB, read now, used after the loop
-    uint64_t pfv = 0;
-    const uint64_t pfb = (uint64_t)blockIdx.x + 8ull * NEXG_SPAN_PF;
-    if (a.offsets && !a.lengths && !(a.hints & NEXG_FRAMES_OFFSETS32) && pfb < gridDim.x && t < 33u) {
-        const uint64_t pg = tile_of((uint32_t)pfb, gridDim.x, a.tile_order) * kTile + 8u * t;
-        if (pg <= a.count) pfv = NEXG_GLOBAL(uint64_t, a.offsets)[pg];
-    }
-#endif
     const bool ok = have && frame_extent(a, idx, off, len);
     if (t == 0) s_span[0] = off;
     if (t == nf - 1) s_span[1] = off + len;
@@ -738,23 +723,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     // range of the batch, so every load stays inside its 16-B blocks
     constexpr int CPT = SUB / 4096u;  // 16-B chunks per thread per sub-tile
     uint4 cur[CPT];
-#if NEXG_SPAN_DEPTH == 2
-    uint4 nxt[CPT];
-#endif
     auto fetch = [&](uint32_t S, uint4 (&v)[CPT]) {
 #pragma unroll
         for (int i = 0; i < CPT; i++) {
             const uint32_t c = S + 16u * (t + 256u * i);
-            v[i] = c < span ? load16g<NEXG_SPAN_NT>(A0 + c) : make_uint4(0, 0, 0, 0);
+            v[i] = c < span ? load16g<true>(A0 + c) : make_uint4(0, 0, 0, 0);
         }
     };
     const bool plausible = hi >= lo && hi <= a.data_bytes && hi - lo <= (1ull << 30);
-    if (plausible) {
-        fetch(0, cur);
-#if NEXG_SPAN_DEPTH == 2
-        fetch(SUB, nxt);  // (chunks past the span load nothing)
-#endif
-    }
+    if (plausible) fetch(0, cur);
     // packed contract: every frame of the group lies inside [lo, hi], and the
     // span is small enough for 32-bit span-relative arithmetic
     const bool inside = !have || (ok && off >= lo && off + len <= hi);
@@ -790,17 +767,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
 #pragma unroll
     for (int j = 0; j < (int)NW; j++) u[j] = 0;
 
-    uint32_t buf = 0;
     // one sub-tile: stage v (this sub-tile's chunks) into LDS, refill v with the
-    // sub-tile NEXG_SPAN_DEPTH ahead, scan, gather
+    // next sub-tile, scan, gather
     auto sub_tile = [&](const uint32_t S, uint4 (&v)[CPT]) {
-        uint8_t* sb = s_bytes[buf] + kApron;
-        uint32_t* sp = s_pfx[buf];
+        uint8_t* sb = s_bytes + kApron;
+        uint32_t* sp = s_pfx;
         // (1) stage bytes + chunk sums, put the next sub-tile in flight. The
         // threads owning the last 6 chunks first move the previous sub-tile's
-        // (NB = 1: this buffer's, before they overwrite it) into the apron.
+        // (still in the buffer, before they overwrite it) into the apron.
         if (S > 0 && t >= kTile - kApron / 16u) {
-            const uint8_t* prev = s_bytes[NB == 2 ? buf ^ 1u : buf] + kApron + SUB - kApron;
+            const uint8_t* prev = s_bytes + kApron + SUB - kApron;
             *reinterpret_cast<uint4*>(sb - kApron + 16u * (t - (kTile - kApron / 16u))) =
                 *reinterpret_cast<const uint4*>(prev + 16u * (t - (kTile - kApron / 16u)));
         }
@@ -811,7 +787,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
             sp[c] = chunk_le_sum(v[i]);
         }
         const uint32_t E = S + SUB;
-        if (S + NEXG_SPAN_DEPTH * SUB < span) fetch(S + NEXG_SPAN_DEPTH * SUB, v);
+        if (S + SUB < span) fetch(S + SUB, v);
         __syncthreads();
         // (2) block exclusive scan of the 1024 chunk sums (4 consecutive per thread)
         uint32_t cs[CPT];
@@ -819,9 +795,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
 #pragma unroll
         for (int i = 0; i < CPT; i++) own += (cs[i] = sp[CPT * t + i]);
         const uint32_t incl = wave_incl_scan_dpp(own);
-        if (lane == 63u) s_wsum[buf][wv] = incl;
+        if (lane == 63u) s_wsum[wv] = incl;
         __syncthreads();
-        const uint4 ws = *reinterpret_cast<const uint4*>(s_wsum[buf]);
+        const uint4 ws = *reinterpret_cast<const uint4*>(s_wsum);
         const uint32_t wbase = (wv > 0 ? ws.x : 0u) + (wv > 1 ? ws.y : 0u) + (wv > 2 ? ws.z : 0u);
         const uint32_t total = ws.x + ws.y + ws.z + ws.w;
         uint32_t ex = wbase + incl - own;
@@ -857,25 +833,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
         if (want_tail && (da < SUB || (last && da == SUB))) qa = q_at(da);
         if (have && (db < SUB || (last && db == SUB))) qb = q_at(db);
         run += total;
-        if (NB == 1) __syncthreads();
+        __syncthreads();  // lookups done: the next sub-tile overwrites the buffer
     };
-#if NEXG_SPAN_DEPTH == 2
-    // two sub-tiles in flight: the loop unrolled by two over two register sets
-    // (a copy between them would wait for the loads in flight)
-    static_assert(NB == 1, "depth 2 runs on one stage buffer");
-    for (uint32_t S = 0; S < span; S += 2u * SUB) {
-        sub_tile(S, cur);
-        if (S + SUB < span) sub_tile(S + SUB, nxt);
-    }
-#else
-    for (uint32_t S = 0; S < span; S += SUB, buf = NB == 2 ? buf ^ 1u : 0u) sub_tile(S, cur);
-#endif
-    if (NB == 2) __syncthreads();  // the stage buffers become per-lane slots below
-#if NEXG_SPAN_PF
-    if (pfv == ~0ull) s_hist[0] = 1u;  // consumes the prefetch (long returned); s_hist is rewritten below
-#endif
+    for (uint32_t S = 0; S < span; S += SUB) sub_tile(S, cur);
     NEXG_SPAN_STAMP(2);
-    uint8_t* const slots = &s_bytes[0][0];  // 80 B per lane from here on
+    uint8_t* const slots = s_bytes;  // 80 B per lane from here on
     // (A) every lane: the canonical fast path on its head window
     uint32_t code = 0, key = 0;
     bool gen = false;
@@ -930,7 +892,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
             s_hist[2 * kBuckets] = acc;
         }
         __syncthreads();
-        uint4* const items = reinterpret_cast<uint4*>(&s_pfx[0][0]);
+        uint4* const items = reinterpret_cast<uint4*>(s_pfx);
         if (gen) items[s_hist[kBuckets + key] + rank] = make_uint4(hr, len | qend << 16, tq, t);
         const uint32_t ngen = s_hist[2 * kBuckets];
         __syncthreads();
@@ -1010,7 +972,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE))) void
     // budget: with them the App. C mix ran 10 % slower, profiles/r03/grouped)
     NEXG_SPAN_STAMP(4);
     if (sparse_like(OUT)) store_sparse_coded<OUT, false>(a, idx, have, r, code);
-    else if (OUT == NEXG_OUT_DESC && NEXG_DESC_MODE == 2) {  // 256 x 8 B through the slots: 16-B NT stores
+    else if (OUT == NEXG_OUT_DESC) {  // 256 x 8 B through the slots: 16-B NT stores
         // own slot only (the generic section's reads of other lanes' slots
         // ended at its last barrier)
         if (have) stage_desc(slots + SpanFrame::kSlot * t, r);

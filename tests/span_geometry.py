@@ -19,7 +19,7 @@ import numpy as np
 
 from nex_amd import abi
 
-SPAN_SUB = {"record": 16384, "other": 24576}  # k_parse_span<RECORD, 1, 16384, 1> / NEXG_SPAN_SUB
+SPAN_SUB = {"record": 16384, "other": 24576}  # k_parse_span<RECORD, 16384, 1> / NEXG_SPAN_SUB
 WIN = 84          # head-window gather: 21 dwords
 SLOT = 80         # NEXG_SPAN_SLOT
 LANE_WIN = 80     # kLaneWin

@@ -30,7 +30,7 @@ def _src(name):
 def test_constants_are_the_sources():
     parse, kern, core = _src("nexg_parse.hip"), _src("parse_kernels.hpp"), _src("frame_core.hpp")
     assert int(re.search(r"#define NEXG_SPAN_SUB (\d+)", parse).group(1)) == sg.SPAN_SUB["other"]
-    assert f"k_parse_span<OUT, 1, {sg.SPAN_SUB['record']}, 1>" in parse
+    assert f"k_parse_span<OUT, {sg.SPAN_SUB['record']}, 1>" in parse
     assert int(re.search(r"#define NEXG_SPAN_SLOT (\d+)", core).group(1)) == sg.SLOT
     assert int(re.search(r"constexpr uint32_t kDefer = (\d+);", core).group(1)) == sg.K_DEFER
     m = re.search(r"constexpr uint32_t kApron = NEXG_SPAN_SLOT > (\d+) \? NEXG_SPAN_SLOT : (\d+);", kern)

@@ -10,7 +10,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-name = sys.argv[1] if len(sys.argv) > 1 else "k_parse_spanILi6ELi1ELj20480ELi6E"
+name = sys.argv[1] if len(sys.argv) > 1 else "k_parse_spanILi6ELj24576ELi5ELb0E"
 out = "/tmp/nexg_parse_isa.s"
 subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950"] + os.environ.get("NEXG_DEFS", "").split() + [
                        "--cuda-device-only", "-S", "-o", out,

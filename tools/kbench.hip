@@ -374,8 +374,7 @@ int main(int argc, char** argv) {
         vars.push_back({"sparse_fast_nt", [=]() { hipLaunchKernelGGL((k_parse<0, NEXG_OUT_SPARSE, 64, 64, true, true>), grid, blk, 0, 0, sa); }, count * 64.0});
     }
     vars.push_back({"prod_generic", parse(k_parse<0, NEXG_OUT_DESC, 64, 64, false, false>), count * 64.0});
-    vars.push_back({"span_udp64_nb2", parse(k_parse_span<NEXG_OUT_DESC, 2>), count * 64.0});
-    vars.push_back({"span_udp64_nb1", parse(k_parse_span<NEXG_OUT_DESC, 1>), count * 64.0});
+    vars.push_back({"span_udp64_nb1", parse(k_parse_span<NEXG_OUT_DESC>), count * 64.0});
     vars.push_back({"lanewindow_generic", parse(k_parse<1, NEXG_OUT_DESC, 0, 128, false, false>), count * 64.0});
     vars.push_back({"lane_direct_fast", [=]() { hipLaunchKernelGGL(k_lanedirect, grid, blk, 0, 0, data, count, out, 0u); }, count * 64.0});
     vars.push_back({"stage_only", [=]() { hipLaunchKernelGGL(k_stageonly, grid, blk, 0, 0, data, count, out); }, count * 64.0});
@@ -436,9 +435,8 @@ int main(int argc, char** argv) {
     ivars.push_back({"imix_2pass_u4", [=]() {
         hipLaunchKernelGGL((k_tail_sums<NEXG_OUT_DESC, 4>), grid, blk, 0, 0, ia);
         hipLaunchKernelGGL(k_parse_lane80<NEXG_OUT_DESC>, grid, blk, 0, 0, ia); }, ibytes});
-    ivars.push_back({"imix_span_nb2", iparse(k_parse_span<NEXG_OUT_DESC, 2>), ibytes});
-    ivars.push_back({"imix_flags_span_nb1", iparse(k_parse_span<NEXG_OUT_FLAGS, 1>), ibytes});
-    ivars.push_back({"imix_span_nb1", iparse(k_parse_span<NEXG_OUT_DESC, 1>), ibytes});
+    ivars.push_back({"imix_flags_span_nb1", iparse(k_parse_span<NEXG_OUT_FLAGS>), ibytes});
+    ivars.push_back({"imix_span_nb1", iparse(k_parse_span<NEXG_OUT_DESC>), ibytes});
     ivars.push_back({"imix_span2_16k", iparse(k_parse_span2<NEXG_OUT_DESC, 16384, 1>), ibytes});
     ivars.push_back({"imix_span2_16k_w6", iparse(k_parse_span2<NEXG_OUT_DESC, 16384, 1, 6>), ibytes});
     ivars.push_back({"imix_span2_8k_nb2", iparse(k_parse_span2<NEXG_OUT_DESC, 8192, 2>), ibytes});
@@ -449,26 +447,25 @@ int main(int argc, char** argv) {
         sa.out = sparse_out;
         ivars.push_back({"imix_sparse_span2_16k", [=]() { hipLaunchKernelGGL((k_parse_span2<NEXG_OUT_SPARSE, 16384, 1>), grid, blk, 0, 0, sa); }, ibytes});
         ivars.push_back({"imix_sparse_span2_8k_nb2", [=]() { hipLaunchKernelGGL((k_parse_span2<NEXG_OUT_SPARSE, 8192, 2>), grid, blk, 0, 0, sa); }, ibytes});
-        ivars.push_back({"imix_sparse_span_v1", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 1>), grid, blk, 0, 0, sa); }, ibytes});
-        ivars.push_back({"imix_sparse_span_v1_w7", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 1, 16384, 7>), grid, blk, 0, 0, sa); }, ibytes});
-        ivars.push_back({"imix_sparse_span_v1_w6", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 1, 16384, 6>), grid, blk, 0, 0, sa); }, ibytes});
+        ivars.push_back({"imix_sparse_span_v1", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE>), grid, blk, 0, 0, sa); }, ibytes});
+        ivars.push_back({"imix_sparse_span_v1_w7", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 16384, 7>), grid, blk, 0, 0, sa); }, ibytes});
+        ivars.push_back({"imix_sparse_span_v1_w6", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 16384, 6>), grid, blk, 0, 0, sa); }, ibytes});
         // larger sub-tiles: more bytes in flight per workgroup, fewer workgroups per CU
-        ivars.push_back({"imix_sparse_span_20k_w6", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 1, 20480, 6>), grid, blk, 0, 0, sa); }, ibytes});
-        ivars.push_back({"imix_sparse_span_20k_w5", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 1, 20480, 5>), grid, blk, 0, 0, sa); }, ibytes});
-        ivars.push_back({"imix_sparse_span_24k_w5", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 1, 24576, 5>), grid, blk, 0, 0, sa); }, ibytes});
-        ivars.push_back({"imix_sparse_span_24k_w4", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 1, 24576, 4>), grid, blk, 0, 0, sa); }, ibytes});
-        ivars.push_back({"imix_sparse_span_28k_w5", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 1, 28672, 5>), grid, blk, 0, 0, sa); }, ibytes});
-        ivars.push_back({"imix_sparse_span_32k_w4", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 1, 32768, 4>), grid, blk, 0, 0, sa); }, ibytes});
-        ivars.push_back({"imix_sparse_span_32k_w5", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 1, 32768, 5>), grid, blk, 0, 0, sa); }, ibytes});
-        ivars.push_back({"imix_desc_span_20k_w6", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_DESC, 1, 20480, 6>), grid, blk, 0, 0, ia); }, ibytes});
-        ivars.push_back({"imix_desc_span_16k_w6", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_DESC, 1, 16384, 6>), grid, blk, 0, 0, ia); }, ibytes});
+        ivars.push_back({"imix_sparse_span_20k_w6", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 20480, 6>), grid, blk, 0, 0, sa); }, ibytes});
+        ivars.push_back({"imix_sparse_span_20k_w5", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 20480, 5>), grid, blk, 0, 0, sa); }, ibytes});
+        ivars.push_back({"imix_sparse_span_24k_w5", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 24576, 5>), grid, blk, 0, 0, sa); }, ibytes});
+        ivars.push_back({"imix_sparse_span_24k_w4", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 24576, 4>), grid, blk, 0, 0, sa); }, ibytes});
+        ivars.push_back({"imix_sparse_span_28k_w5", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 28672, 5>), grid, blk, 0, 0, sa); }, ibytes});
+        ivars.push_back({"imix_sparse_span_32k_w4", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 32768, 4>), grid, blk, 0, 0, sa); }, ibytes});
+        ivars.push_back({"imix_sparse_span_32k_w5", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_SPARSE, 32768, 5>), grid, blk, 0, 0, sa); }, ibytes});
+        ivars.push_back({"imix_desc_span_20k_w6", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_DESC, 20480, 6>), grid, blk, 0, 0, ia); }, ibytes});
+        ivars.push_back({"imix_desc_span_16k_w6", [=]() { hipLaunchKernelGGL((k_parse_span<NEXG_OUT_DESC, 16384, 6>), grid, blk, 0, 0, ia); }, ibytes});
     }
-    ivars.push_back({"imix_span_nb1_8k", iparse(k_parse_span<NEXG_OUT_DESC, 1, 8192>), ibytes});
-    ivars.push_back({"imix_span_nb2_8k", iparse(k_parse_span<NEXG_OUT_DESC, 2, 8192>), ibytes});
-    ivars.push_back({"imix_span_nb1_32k", iparse(k_parse_span<NEXG_OUT_DESC, 1, 32768>), ibytes});
+    ivars.push_back({"imix_span_nb1_8k", iparse(k_parse_span<NEXG_OUT_DESC, 8192>), ibytes});
+    ivars.push_back({"imix_span_nb1_32k", iparse(k_parse_span<NEXG_OUT_DESC, 32768>), ibytes});
     ivars.push_back({"imix_span_rec", [=]() {
         ParseArgs r2 = ia; r2.out = rec;
-        hipLaunchKernelGGL((k_parse_span<NEXG_OUT_RECORD, 1>), grid, blk, 0, 0, r2); }, ibytes});
+        hipLaunchKernelGGL((k_parse_span<NEXG_OUT_RECORD>), grid, blk, 0, 0, r2); }, ibytes});
     ivars.push_back({"ABL_span_stage", iparse(k_span_skeleton<0>), ibytes});
     ivars.push_back({"ABL_span_stage_scan", iparse(k_span_skeleton<1>), ibytes});
     ivars.push_back({"ABL_span_stage_scan_head", iparse(k_span_skeleton<2>), ibytes});

@@ -35,6 +35,8 @@ def kernels(src, defs):
             cur[m.group(2).strip()] = int(m.group(3))
     asm = p.stdout
     names = re.findall(r"^\s*\.amdhsa_kernel (\S+)", asm, re.M)
+    if not names:  # a source without kernels (c++filt without arguments would wait on stdin)
+        return
     demangled = subprocess.run(["c++filt"] + names, capture_output=True, text=True,
                                check=True).stdout.splitlines()
     for name, dm in zip(names, demangled):
