@@ -1371,10 +1371,7 @@ class Engine {  // one nexg context on one gfx950 device, one stream
         check(nexg_decap_select(ctx_, tunnels, inner_off, inner_len, count, inner_mask, out_index, out_off, out_len,
                                 d_count, ws, wsb, stream_),
               "nexg_decap_select");
-        uint64_t k = 0;
-        check_hip(hipMemcpyAsync(&k, d_count, 8, hipMemcpyDeviceToHost, stream_), "D2H");
-        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-        return k;
+        return read_u64(d_count);
     }
 
     // The tunnel of every host frame: parse (NEXG_OUT_RECORD) + decap on the
@@ -1489,10 +1486,7 @@ class Engine {  // one nexg context on one gfx950 device, one stream
         check(nexg_select_batch(ctx_, &frames, records, &filter.get(), out_index, out_off, out_len, out_rule, d_count,
                                 ws, wsb, stream_),
               "nexg_select_batch");
-        uint64_t k = 0;
-        check_hip(hipMemcpyAsync(&k, d_count, 8, hipMemcpyDeviceToHost, stream_), "D2H");
-        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-        return k;
+        return read_u64(d_count);
     }
 
     // Where gather puts each frame of `sel` (nexg_gather_plan): out_offsets
@@ -1503,10 +1497,7 @@ class Engine {  // one nexg context on one gfx950 device, one stream
         const uint64_t wsb = nexg_gather_plan_workspace(sel.count);
         void* ws = scratch(23, wsb);
         check(nexg_gather_plan(ctx_, &sel, align, out_offsets, out_len, ws, wsb, stream_), "nexg_gather_plan");
-        uint64_t total = 0;
-        check_hip(hipMemcpyAsync(&total, out_offsets + sel.count, 8, hipMemcpyDeviceToHost, stream_), "D2H");
-        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-        return total;
+        return read_u64(out_offsets + sel.count);
     }
 
     // The frames of `sel` copied to out_data at the planned offsets, pads
@@ -1605,10 +1596,7 @@ class Engine {  // one nexg context on one gfx950 device, one stream
         check(nexg_match_select(ctx_, &frames, matches, any_mask, all_mask, none_mask, out_index, out_off, out_len, d_count,
                                 ws, wsb, stream_),
               "nexg_match_select");
-        uint64_t k = 0;
-        check_hip(hipMemcpyAsync(&k, d_count, 8, hipMemcpyDeviceToHost, stream_), "D2H");
-        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-        return k;
+        return read_u64(d_count);
     }
 
     // parse (NEXG_OUT_RECORD) + match + match_select of host frames: every
@@ -1739,10 +1727,7 @@ class Engine {  // one nexg context on one gfx950 device, one stream
         check(nexg_flow_groups(ctx_, &frames, records, flows, &option.get(), order, out, cap, out_group, d_count, ws, wsb,
                                stream_),
               "nexg_flow_groups");
-        uint64_t n = 0;
-        check_hip(hipMemcpyAsync(&n, d_count, 8, hipMemcpyDeviceToHost, stream_), "D2H");
-        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-        return n;
+        return read_u64(d_count);
     }
 
     // parse (NEXG_OUT_RECORD) + flow + flow_sort + flow_groups of host frames
@@ -1797,10 +1782,7 @@ class Engine {  // one nexg context on one gfx950 device, one stream
         check(nexg_flow_table_merge(ctx_, &frames, records, &option.get(), groups, n_groups, table_in, n_in, epoch,
                                     min_epoch, table_out, cap, out_slot, d_count, ws, wsb, stream_),
               "nexg_flow_table_merge");
-        uint64_t n = 0;
-        check_hip(hipMemcpyAsync(&n, d_count, 8, hipMemcpyDeviceToHost, stream_), "D2H");
-        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-        return n;
+        return read_u64(d_count);
     }
 
     // parse (NEXG_OUT_RECORD) + flow + flow_sort + flow_groups of host frames,
@@ -2218,10 +2200,7 @@ class Engine {  // one nexg context on one gfx950 device, one stream
         void* ws = scratch(48, wsb);
         check(nexg_encap_plan(ctx_, &frames, &tunnels.get(), tunnel_index, align, out_offsets, out_len, ws, wsb, stream_),
               "nexg_encap_plan");
-        uint64_t total = 0;
-        check_hip(hipMemcpyAsync(&total, out_offsets + frames.count, 8, hipMemcpyDeviceToHost, stream_), "D2H");
-        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-        return total;
+        return read_u64(out_offsets + frames.count);
     }
 
     // Every frame behind its tunnel's outer Ethernet / IP / UDP + VXLAN or GRE
@@ -2424,6 +2403,13 @@ class Engine {  // one nexg context on one gfx950 device, one stream
             b.size = n ? n : 16;
         }
         return b.p;
+    }
+    // one count or total a call left in device memory; waits for the stream
+    uint64_t read_u64(const uint64_t* device) {
+        uint64_t v = 0;
+        check_hip(hipMemcpyAsync(&v, device, 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        return v;
     }
     // host frames packed (4-B aligned starts) with offsets + lengths, on the device
     struct HostBatch {

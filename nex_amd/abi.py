@@ -409,8 +409,7 @@ class DecapOption(ctypes.Structure):
 
 def decap_select_workspace(count):
     """nexg_decap_select_workspace: bytes of nexg_decap_select's workspace."""
-    tiles = (int(count) + 255) // 256
-    return 4 * ((tiles + 255) // 256 * 256) + 16
+    return select_workspace(count)
 
 
 # tunnel encapsulation (nexg_encap_plan / nexg_encap_frames; an extension: the

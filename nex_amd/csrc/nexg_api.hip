@@ -343,8 +343,7 @@ int nexg_decap_select(nexg_ctx* ctx, const nexg_tunnel* tunnels, const uint64_t*
         return fail(ctx, NEXG_EINVAL, "misaligned input, output or workspace%s", nullptr);
     DeviceGuard g(ctx);
     return launched(ctx, nexg::launch_decap_select(tunnels, inner_off, inner_len, count, inner_mask, out_index, out_off,
-                                                   out_len, out_count, static_cast<uint32_t*>(workspace),
-                                                   as_stream(stream)));
+                                                   out_len, out_count, workspace, as_stream(stream)));
 }
 
 int nexg_dns_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_record* records,
@@ -408,7 +407,7 @@ int nexg_select_batch(nexg_ctx* ctx, const nexg_frames* frames, const nexg_recor
     const nexg::ParseArgs a = to_args(frames);
     DeviceGuard g(ctx);
     return launched(ctx, nexg::launch_select(a, records, f, out_index, out_off, out_len, out_rule, out_count,
-                                             static_cast<uint32_t*>(workspace), as_stream(stream)));
+                                             workspace, as_stream(stream)));
 }
 
 int nexg_patterns_check(const nexg_patterns* set) {
@@ -469,8 +468,7 @@ int nexg_gather_plan(nexg_ctx* ctx, const nexg_frames* sel, uint32_t align, uint
         return fail(ctx, NEXG_EINVAL, "misaligned output or workspace%s", nullptr);
     const nexg::ParseArgs a = to_args(sel);
     DeviceGuard g(ctx);
-    return launched(ctx, nexg::launch_gather_plan(a, align, out_offsets, out_len, static_cast<uint64_t*>(workspace),
-                                                  as_stream(stream)));
+    return launched(ctx, nexg::launch_gather_plan(a, align, out_offsets, out_len, workspace, as_stream(stream)));
 }
 
 int nexg_gather_frames(nexg_ctx* ctx, const nexg_frames* sel, const uint64_t* out_offsets, uint8_t* out_data,
@@ -509,7 +507,7 @@ int nexg_encap_plan(nexg_ctx* ctx, const nexg_frames* frames, const nexg_tunnels
     const nexg::ParseArgs a = to_args(frames);
     DeviceGuard g(ctx);
     return launched(ctx, nexg::launch_encap_plan(a, es, tunnel_index, align, out_offsets, out_len,
-                                                 static_cast<uint64_t*>(workspace), as_stream(stream)));
+                                                 workspace, as_stream(stream)));
 }
 
 int nexg_encap_frames(nexg_ctx* ctx, const nexg_frames* frames, const nexg_tunnels* set, const uint8_t* tunnel_index,

@@ -6,7 +6,8 @@
 // result by inner class. No frame byte is copied: the outputs are offset +
 // length tables over the outer batch's data that nexg_parse_batch takes as
 // they stand. Record fields, the header bytes as big-endian words and the
-// compaction's count / rank / scan come from table_kernels.hpp.
+// compaction itself (count, scan, scatter) come from table_kernels.hpp: the
+// select is its rule on a nexg_tunnel's first dword.
 #include "table_kernels.hpp"
 
 namespace nexg {
@@ -82,58 +83,34 @@ hipError_t launch_decap(const ParseArgs& a, const nexg_record* recs, uint32_t wh
     return hipGetLastError();
 }
 
-// ---- nexg_decap_select: count per 256-frame tile (block_count), scan of the
-// tile counts (k_tile_scan), scatter by rank. Positions come from ballots,
-// mbcnt ranks and scans alone.
+// ---- nexg_decap_select: table_kernels.hpp's compaction with this selector ----
 
-// first dword of a nexg_tunnel: kind | status << 8 | inner << 16 | hdr_len << 24
-__device__ __forceinline__ bool decap_selected(const nexg_tunnel* tunnels, uint64_t idx, uint64_t count,
-                                               uint32_t inner_mask) {
-    if (idx >= count) return false;
-    const uint32_t h = NEXG_GLOBAL(uint32_t, tunnels)[idx * 4u];
-    const uint32_t inner = (h >> 16) & 0xFFu;
-    return (h & 0xFFu) != 0u && (h & 0xFF00u) == 0u && inner < 32u && ((inner_mask >> inner) & 1u) != 0u;
-}
-
-__global__ __launch_bounds__(256) void k_decap_count(const nexg_tunnel* tunnels, uint64_t count, uint32_t inner_mask,
-                                                     uint32_t* tile_count) {
-    __shared__ uint32_t s_w[4];
-    const uint64_t idx = (uint64_t)blockIdx.x * kTile + threadIdx.x;
-    const uint32_t total = block_count(decap_selected(tunnels, idx, count, inner_mask), s_w).total;
-    if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(256) void k_decap_scatter(const nexg_tunnel* tunnels, const uint64_t* inner_off,
-                                                       const uint32_t* inner_len, uint64_t count, uint32_t inner_mask,
-                                                       const uint32_t* tile_base, uint32_t* out_index, uint64_t* out_off,
-                                                       uint32_t* out_len) {
-    __shared__ uint32_t s_w[4];
-    const uint64_t idx = (uint64_t)blockIdx.x * kTile + threadIdx.x;
-    const bool sel = decap_selected(tunnels, idx, count, inner_mask);
-    const uint32_t rank = block_count(sel, s_w).rank;
-    if (!sel) return;
-    // rank < the number selected <= count: inside the outputs' capacity (checked
-    // all the same: a caller rewriting `tunnels` between the passes must not
-    // turn into a store out of bounds)
-    const uint64_t k = (uint64_t)tile_base[blockIdx.x] + rank;
-    if (k >= count) return;
-    out_index[k] = (uint32_t)idx;
-    out_off[k] = NEXG_GLOBAL(uint64_t, inner_off)[idx];
-    out_len[k] = NEXG_GLOBAL(uint32_t, inner_len)[idx];
-}
+struct DecapPick {
+    const nexg_tunnel* tunnels;
+    const uint64_t* inner_off;
+    const uint32_t* inner_len;
+    uint64_t n;
+    uint32_t inner_mask;
+    struct Picked {};
+    static constexpr bool kTagged = false;
+    NEXG_HD uint64_t count() const { return n; }
+    // first dword of a nexg_tunnel: kind | status << 8 | inner << 16 | hdr_len << 24
+    __device__ __forceinline__ bool pick(uint64_t idx, Picked&) const {
+        const uint32_t h = NEXG_GLOBAL(uint32_t, tunnels)[idx * 4u];
+        const uint32_t inner = (h >> 16) & 0xFFu;
+        return (h & 0xFFu) != 0u && (h & 0xFF00u) == 0u && inner < 32u && ((inner_mask >> inner) & 1u) != 0u;
+    }
+    __device__ __forceinline__ void entry(uint64_t idx, const Picked&, uint64_t& off, uint32_t& len) const {
+        off = NEXG_GLOBAL(uint64_t, inner_off)[idx];
+        len = NEXG_GLOBAL(uint32_t, inner_len)[idx];
+    }
+};
 
 hipError_t launch_decap_select(const nexg_tunnel* tunnels, const uint64_t* inner_off, const uint32_t* inner_len,
                                uint64_t count, uint32_t inner_mask, uint32_t* out_index, uint64_t* out_off,
-                               uint32_t* out_len, uint64_t* out_count, uint32_t* tile_count, hipStream_t s) {
-    const uint64_t tiles = (count + kTile - 1) / kTile;
-    if (tiles)
-        hipLaunchKernelGGL(k_decap_count, dim3((uint32_t)tiles), dim3(kTile), 0, s, tunnels, count, inner_mask,
-                           tile_count);
-    hipLaunchKernelGGL(k_tile_scan<uint32_t>, dim3(1), dim3(kTile), 0, s, tile_count, tiles, out_count);
-    if (tiles)
-        hipLaunchKernelGGL(k_decap_scatter, dim3((uint32_t)tiles), dim3(kTile), 0, s, tunnels, inner_off, inner_len,
-                           count, inner_mask, tile_count, out_index, out_off, out_len);
-    return hipGetLastError();
+                               uint32_t* out_len, uint64_t* out_count, void* workspace, hipStream_t s) {
+    return launch_compact(DecapPick{tunnels, inner_off, inner_len, count, inner_mask}, out_index, out_off, out_len,
+                          nullptr, out_count, workspace, s);
 }
 
 }  // namespace nexg

@@ -79,11 +79,13 @@ __global__ __launch_bounds__(256) void k_encap_plan_write(ParseArgs a, EncapPlan
 }
 
 hipError_t launch_encap_plan(const ParseArgs& a, const EncapSet& set, const uint8_t* tunnel_index, uint32_t align,
-                             uint64_t* out_offsets, uint32_t* out_len, uint64_t* tile_sum, hipStream_t st) {
+                             uint64_t* out_offsets, uint32_t* out_len, void* workspace, hipStream_t st) {
     EncapPlanSet s{};
     s.n = set.n;
     for (uint32_t i = 0; i < set.n; i++) s.meta[i] = set.t[i].meta;
-    const uint64_t tiles = (a.count + kTile - 1) / kTile;
+    const TileSumLayout w = TileSumLayout::from(a.count);
+    const uint64_t tiles = w.tiles;
+    uint64_t* tile_sum = region<uint64_t>(workspace, w.tile_sum);
     if (tiles) hipLaunchKernelGGL(k_encap_plan_sum, dim3((uint32_t)tiles), dim3(kTile), 0, st, a, s, tunnel_index, align, tile_sum);
     hipLaunchKernelGGL(k_tile_scan<uint64_t>, dim3(1), dim3(kTile), 0, st, tile_sum, tiles, out_offsets + a.count);
     if (tiles)

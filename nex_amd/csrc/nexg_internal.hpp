@@ -106,22 +106,22 @@ hipError_t launch_rewrite(const ParseArgs& a, const nexg_actions& actions, const
 hipError_t launch_decode_options(const ParseArgs& a, const nexg_record* recs, nexg_options* out,
                                  hipStream_t s);
 
-// nexg_decap_batch / nexg_decap_select (nexg_decap.hip). tile_count: one u32
-// per 256-frame tile (the caller's workspace), left holding the tiles'
-// exclusive scan.
+// nexg_decap_batch / nexg_decap_select (nexg_decap.hip). workspace: as
+// nexg_decap_select_workspace sizes it (workspace_layout.hpp TileCountLayout),
+// left holding the tiles' exclusive scan.
 hipError_t launch_decap(const ParseArgs& a, const nexg_record* recs, uint32_t which, uint32_t vxlan_port,
                         nexg_tunnel* tunnels, uint64_t* inner_off, uint32_t* inner_len, hipStream_t s);
 hipError_t launch_decap_select(const nexg_tunnel* tunnels, const uint64_t* inner_off, const uint32_t* inner_len,
                                uint64_t count, uint32_t inner_mask, uint32_t* out_index, uint64_t* out_off,
-                               uint32_t* out_len, uint64_t* out_count, uint32_t* tile_count, hipStream_t s);
+                               uint32_t* out_len, uint64_t* out_count, void* workspace, hipStream_t s);
 
 // nexg_encap_plan / nexg_encap_frames (nexg_encap.hip). The specs travel as a
 // kernel argument in the form encap_core.hpp's prepare_tunnels gives them.
-// tile_sum: one u64 per 256-frame tile (the caller's workspace), left holding
-// the tiles' exclusive scan.
+// workspace: as nexg_encap_plan_workspace sizes it (workspace_layout.hpp
+// TileSumLayout), left holding the tiles' exclusive scan.
 struct EncapSet;
 hipError_t launch_encap_plan(const ParseArgs& a, const EncapSet& set, const uint8_t* tunnel_index, uint32_t align,
-                             uint64_t* out_offsets, uint32_t* out_len, uint64_t* tile_sum, hipStream_t s);
+                             uint64_t* out_offsets, uint32_t* out_len, void* workspace, hipStream_t s);
 hipError_t launch_encap_frames(const ParseArgs& a, const EncapSet& set, const uint8_t* tunnel_index, const nexg_flow* flows,
                                const uint64_t* out_offsets, uint8_t* out_data, uint64_t out_cap, nexg_encapped* rows,
                                hipStream_t s);
@@ -160,11 +160,14 @@ struct SelFilter {
 };
 // nullptr when the filter is valid (then *out, if given, is filled), else what is wrong with it
 const char* prepare_filter(const nexg_filter* f, SelFilter* out);
+// workspace: as nexg_select_workspace (workspace_layout.hpp TileCountLayout) and
+// nexg_gather_plan_workspace (TileSumLayout) size it, left holding the tiles'
+// exclusive scan
 hipError_t launch_select(const ParseArgs& a, const nexg_record* recs, const SelFilter& f, uint32_t* out_index,
                          uint64_t* out_off, uint32_t* out_len, uint8_t* out_rule, uint64_t* out_count,
-                         uint32_t* tile_count, hipStream_t s);
+                         void* workspace, hipStream_t s);
 hipError_t launch_gather_plan(const ParseArgs& a, uint32_t align, uint64_t* out_offsets, uint32_t* out_len,
-                              uint64_t* tile_sum, hipStream_t s);
+                              void* workspace, hipStream_t s);
 hipError_t launch_gather_frames(const ParseArgs& a, const uint64_t* out_offsets, uint8_t* out_data, uint64_t out_cap,
                                 hipStream_t s);
 hipError_t launch_gather_rows(const void* rows, uint32_t row_bytes, uint64_t rows_count, const uint32_t* index,
@@ -172,7 +175,7 @@ hipError_t launch_gather_rows(const void* rows, uint32_t row_bytes, uint64_t row
 
 // nexg_match_batch / nexg_match_select (nexg_match.hip). The set travels as a
 // kernel argument in the form match_core.hpp gives it. workspace: as
-// nexg_match_select_workspace sizes it (workspace_layout.hpp MatchSelectLayout),
+// nexg_match_select_workspace sizes it (workspace_layout.hpp TileCountLayout),
 // left holding the tiles' exclusive scan.
 struct MatchSet;
 hipError_t launch_match(const ParseArgs& a, const nexg_record* recs, const MatchSet& s, nexg_match* out, hipStream_t st);

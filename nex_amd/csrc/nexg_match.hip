@@ -4,8 +4,11 @@
 // patterns at every start position behind a two-byte prefilter; the per-frame
 // rule (region, fold, occurrence, row) is match_core.hpp's, which the host
 // driver tests/native/match_fuzz.cpp runs too. k_match_count / k_tile_scan /
-// k_match_scatter compact the frame table by the rows' masks in order, in the
-// shape of nexg_select_batch on the same primitives of table_kernels.hpp.
+// k_match_scatter compact the frame table by the rows' masks in order. That is
+// table_kernels.hpp's compaction written out: as the selector MatchPick of
+// launch_compact the pass measured 0.7 to 1 % slower (the count kernel, which
+// reads a count, a pointer and three masks, got the whole ParseArgs as its
+// argument; profiles/table_skeletons/README.md), so it keeps its own kernels.
 #include "match_core.hpp"
 #include "table_kernels.hpp"
 #include "workspace_layout.hpp"
@@ -207,7 +210,7 @@ __global__ __launch_bounds__(256) void k_match_scatter(ParseArgs a, const nexg_m
 hipError_t launch_match_select(const ParseArgs& a, const nexg_match* rows, uint32_t any_mask, uint32_t all_mask,
                                uint32_t none_mask, uint32_t* out_index, uint64_t* out_off, uint32_t* out_len,
                                uint64_t* out_count, void* workspace, hipStream_t s) {
-    const MatchSelectLayout w = MatchSelectLayout::from(a.count);
+    const TileCountLayout w = TileCountLayout::from(a.count);
     const uint64_t tiles = w.tiles;
     uint32_t* tile_count = region<uint32_t>(workspace, w.tile_count);
     const MatchSel m{any_mask, all_mask, none_mask};

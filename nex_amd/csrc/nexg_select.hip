@@ -2,8 +2,7 @@
 // (include/nexg.h; an extension: the reference has no filter). A pass over a
 // batch already parsed with NEXG_OUT_RECORD that tests each frame's record
 // against up to 16 rules and compacts the matching frames' table entries in
-// order (count per 256-frame tile, scan of the tile counts, scatter: the shape
-// of nexg_decap_select, on the same primitives of table_kernels.hpp), then the
+// order (table_kernels.hpp's compaction; the rule is select_rule), then the
 // gather that copies the selected frames into one dense buffer and compacts
 // per-frame rows by the selected index.
 #include "table_kernels.hpp"
@@ -147,60 +146,32 @@ __device__ __forceinline__ uint32_t select_rule(const ParseArgs& a, const nexg_r
     return hit;
 }
 
-struct SelArgs {
+// nexg_select_batch: table_kernels.hpp's compaction with this selector. Off, len
+// and the verdict all come from the one select_rule call of pick().
+struct SelectPick {
     ParseArgs a;
     const nexg_record* recs;
     SelFilter f;
+    struct Picked {
+        uint64_t off = 0;
+        uint32_t len = 0, hit = NEXG_RULE_NONE;
+    };
+    static constexpr bool kTagged = true;  // out_rule
+    NEXG_HD uint64_t count() const { return a.count; }
+    __device__ __forceinline__ bool pick(uint64_t idx, Picked& p) const {
+        p.hit = select_rule(a, recs, f, idx, p.off, p.len);
+        return (p.hit != NEXG_RULE_NONE) != (f.invert != 0u);
+    }
+    __device__ __forceinline__ void entry(uint64_t, const Picked& p, uint64_t& off, uint32_t& len) const {
+        off = p.off, len = p.len;
+    }
+    __device__ __forceinline__ uint8_t tag(const Picked& p) const { return (uint8_t)(f.invert ? NEXG_RULE_NONE : p.hit); }
 };
 
-__global__ __launch_bounds__(256) void k_select_count(SelArgs p, uint32_t* tile_count) {
-    __shared__ uint32_t s_w[4];
-    const uint64_t idx = (uint64_t)blockIdx.x * kTile + threadIdx.x;
-    bool sel = false;
-    if (idx < p.a.count) {
-        uint64_t off;
-        uint32_t len;
-        sel = (select_rule(p.a, p.recs, p.f, idx, off, len) != NEXG_RULE_NONE) != (p.f.invert != 0u);
-    }
-    const uint32_t total = block_count(sel, s_w).total;
-    if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(256) void k_select_scatter(SelArgs p, const uint32_t* tile_base, uint32_t* out_index,
-                                                        uint64_t* out_off, uint32_t* out_len, uint8_t* out_rule) {
-    __shared__ uint32_t s_w[4];
-    const uint64_t idx = (uint64_t)blockIdx.x * kTile + threadIdx.x;
-    bool sel = false;
-    uint64_t off = 0;
-    uint32_t len = 0, hit = NEXG_RULE_NONE;
-    if (idx < p.a.count) {
-        hit = select_rule(p.a, p.recs, p.f, idx, off, len);
-        sel = (hit != NEXG_RULE_NONE) != (p.f.invert != 0u);
-    }
-    const uint32_t rank = block_count(sel, s_w).rank;
-    if (!sel) return;
-    // rank < the number selected <= count: inside the outputs' capacity (checked
-    // all the same: a caller rewriting the records or the workspace between
-    // the passes must not turn into a store out of bounds)
-    const uint64_t k = (uint64_t)tile_base[blockIdx.x] + rank;
-    if (k >= p.a.count) return;
-    out_index[k] = (uint32_t)idx;
-    out_off[k] = off;
-    out_len[k] = len;
-    if (out_rule) out_rule[k] = (uint8_t)(p.f.invert ? NEXG_RULE_NONE : hit);
-}
-
 hipError_t launch_select(const ParseArgs& a, const nexg_record* recs, const SelFilter& f, uint32_t* out_index,
-                         uint64_t* out_off, uint32_t* out_len, uint8_t* out_rule, uint64_t* out_count,
-                         uint32_t* tile_count, hipStream_t s) {
-    const uint64_t tiles = (a.count + kTile - 1) / kTile;
-    SelArgs p{a, recs, f};
-    if (tiles) hipLaunchKernelGGL(k_select_count, dim3((uint32_t)tiles), dim3(kTile), 0, s, p, tile_count);
-    hipLaunchKernelGGL(k_tile_scan<uint32_t>, dim3(1), dim3(kTile), 0, s, tile_count, tiles, out_count);
-    if (tiles)
-        hipLaunchKernelGGL(k_select_scatter, dim3((uint32_t)tiles), dim3(kTile), 0, s, p, tile_count, out_index, out_off,
-                           out_len, out_rule);
-    return hipGetLastError();
+                         uint64_t* out_off, uint32_t* out_len, uint8_t* out_rule, uint64_t* out_count, void* workspace,
+                         hipStream_t s) {
+    return launch_compact(SelectPick{a, recs, f}, out_index, out_off, out_len, out_rule, out_count, workspace, s);
 }
 
 // ---- gather plan -------------------------------------------------------------------
@@ -233,8 +204,10 @@ __global__ __launch_bounds__(256) void k_plan_write(ParseArgs a, uint32_t align,
 }
 
 hipError_t launch_gather_plan(const ParseArgs& a, uint32_t align, uint64_t* out_offsets, uint32_t* out_len,
-                              uint64_t* tile_sum, hipStream_t s) {
-    const uint64_t tiles = (a.count + kTile - 1) / kTile;
+                              void* workspace, hipStream_t s) {
+    const TileSumLayout w = TileSumLayout::from(a.count);
+    const uint64_t tiles = w.tiles;
+    uint64_t* tile_sum = region<uint64_t>(workspace, w.tile_sum);
     if (tiles) hipLaunchKernelGGL(k_plan_sum, dim3((uint32_t)tiles), dim3(kTile), 0, s, a, align, tile_sum);
     hipLaunchKernelGGL(k_tile_scan<uint64_t>, dim3(1), dim3(kTile), 0, s, tile_sum, tiles, out_offsets + a.count);
     if (tiles)

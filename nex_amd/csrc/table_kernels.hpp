@@ -1,13 +1,15 @@
 // table_kernels.hpp — what the second passes share (nexg_decap.hip,
-// nexg_dns.hip, nexg_select.hip, nexg_flow.hip): the record's fields by dword,
-// a frame's table entry as the table gives it, frame bytes as big-endian
-// words, the 256-lane workgroup's scan / count / sum, and the one-workgroup
-// scan of per-tile values.
+// nexg_dns.hip, nexg_select.hip, nexg_flow.hip, ...): the record's fields by
+// dword, a frame's table entry as the table gives it, frame bytes as
+// big-endian words, the 256-lane workgroup's scan / count / sum, the
+// one-workgroup scan of per-tile values, and on top of those the
+// order-preserving compaction of a frame table (decap_select, select).
 #pragma once
 
 #include <cstddef>
 
 #include "parse_kernels.hpp"
+#include "workspace_layout.hpp"
 
 namespace nexg {
 
@@ -53,7 +55,13 @@ __device__ __forceinline__ uint32_t rec_l4_type(uint32_t dw) { return (dw >> 16)
 
 // off(i) and len(i) as the table gives them (frame_extent's reads, without its
 // clamp: the selected table repeats the input's entries); false for an extent
-// nexg_parse_batch reports as NEXG_ERR_BAD_EXTENT
+// nexg_parse_batch reports as NEXG_ERR_BAD_EXTENT.
+// A second reader beside parse_kernels.hpp's frame_extent, on purpose. One
+// reader in frame_extent's five-branch wording, with frame_extent as it plus
+// the clamp, kept every parse kernel's code but made nexg_flow_table_merge
+// 0.7 to 0.85 % slower (k_merge_write; profiles/table_skeletons/README.md),
+// and this wording inside frame_extent changes the parse kernels. A change to
+// the over-4-GiB base arithmetic has to be made in both.
 __device__ __forceinline__ bool table_extent(const ParseArgs& a, uint64_t idx, uint64_t& off, uint64_t& l64) {
     if (a.offsets && !a.lengths && (a.hints & NEXG_FRAMES_OFFSETS32)) {
         const auto* op = NEXG_GLOBAL(uint32_t, a.offsets);
@@ -155,6 +163,69 @@ __global__ __launch_bounds__(256) void k_tile_scan(T* tile, uint64_t tiles, uint
         __syncthreads();  // s_w is rewritten by the next step
     }
     if (t == 0) *out_total = carry;
+}
+
+// ---- order-preserving compaction of a frame table ------------------------------------------
+// Count per 256-frame tile (block_count), scan of the tile counts
+// (k_tile_scan), scatter by rank: positions come from ballots, mbcnt ranks and
+// scans alone, so a run repeats bit for bit. A pass is its selector S, a struct
+// that travels by value as the kernel argument (what it holds stays in scalar
+// registers) and provides
+//   uint64_t count() const                    the frames of the input table (host and device)
+//   struct Picked                             what pick() worked out and entry() wants again; may be empty
+//   bool pick(idx, Picked&) const             is frame idx < count() selected; the only part the count kernel runs
+//   void entry(idx, picked, off, len) const   the selected frame's entry of the output table
+//   static constexpr bool kTagged             whether the pass has the optional per-frame output out_tag (one byte
+//                                             per selected frame, select's out_rule); if so
+//   uint8_t tag(picked) const                 the selected frame's byte of it
+// The workspace is TileCountLayout's, left holding the tiles' exclusive scan.
+
+template <typename S>
+__global__ __launch_bounds__(256) void k_compact_count(S s, uint32_t* tile_count) {
+    __shared__ uint32_t s_w[4];
+    const uint64_t idx = (uint64_t)blockIdx.x * kTile + threadIdx.x;
+    typename S::Picked p;
+    const bool sel = idx < s.count() && s.pick(idx, p);
+    const uint32_t total = block_count(sel, s_w).total;
+    if (threadIdx.x == 0) tile_count[blockIdx.x] = total;
+}
+
+template <typename S>
+__global__ __launch_bounds__(256) void k_compact_scatter(S s, const uint32_t* tile_base, uint32_t* out_index,
+                                                         uint64_t* out_off, uint32_t* out_len, uint8_t* out_tag) {
+    __shared__ uint32_t s_w[4];
+    const uint64_t idx = (uint64_t)blockIdx.x * kTile + threadIdx.x;
+    typename S::Picked p;
+    const bool sel = idx < s.count() && s.pick(idx, p);
+    const uint32_t rank = block_count(sel, s_w).rank;
+    if (!sel) return;
+    // rank < the number selected <= count: inside the outputs' capacity (checked
+    // all the same: a caller rewriting what pick() reads or the workspace
+    // between the passes must not turn into a store out of bounds)
+    const uint64_t k = (uint64_t)tile_base[blockIdx.x] + rank;
+    if (k >= s.count()) return;
+    uint64_t off;
+    uint32_t len;
+    s.entry(idx, p, off, len);
+    out_index[k] = (uint32_t)idx;
+    out_off[k] = off;
+    out_len[k] = len;
+    if constexpr (S::kTagged)
+        if (out_tag) out_tag[k] = s.tag(p);
+}
+
+// an empty table launches the scan alone: *out_count = 0
+template <typename S>
+hipError_t launch_compact(const S& sel, uint32_t* out_index, uint64_t* out_off, uint32_t* out_len, uint8_t* out_tag,
+                          uint64_t* out_count, void* workspace, hipStream_t s) {
+    const TileCountLayout w = TileCountLayout::from(sel.count());
+    uint32_t* tile_count = region<uint32_t>(workspace, w.tile_count);
+    if (w.tiles) hipLaunchKernelGGL(k_compact_count<S>, dim3((uint32_t)w.tiles), dim3(kTile), 0, s, sel, tile_count);
+    hipLaunchKernelGGL(k_tile_scan<uint32_t>, dim3(1), dim3(kTile), 0, s, tile_count, w.tiles, out_count);
+    if (w.tiles)
+        hipLaunchKernelGGL(k_compact_scatter<S>, dim3((uint32_t)w.tiles), dim3(kTile), 0, s, sel, tile_count, out_index,
+                           out_off, out_len, out_tag);
+    return hipGetLastError();
 }
 
 }  // namespace nexg

@@ -2,7 +2,7 @@
 //
 // include/nexg.h gives each workspace's size (the nexg_*_workspace inlines, a C
 // header other people compile); the structs here name the regions inside and
-// give their byte offsets, and the launchers of nexg_flow.hip take every
+// give their byte offsets, and the launchers that take a workspace take every
 // pointer from them. tests/native/workspace_layout_test.cpp holds the two
 // against each other: equal sizes, regions aligned, disjoint and in bounds
 // (FlowTableLayout: tests/test_flow_table_layout.py, through
@@ -20,17 +20,33 @@ inline T* region(void* workspace, uint64_t offset) {
     return reinterpret_cast<T*>(static_cast<char*>(workspace) + offset);
 }
 
-// nexg_match_select_workspace (the nexg_select_workspace formula): one u32 per
+// nexg_select_workspace, nexg_decap_select_workspace and
+// nexg_match_select_workspace (the order-preserving compactions): one u32 per
 // 256-frame tile, rounded up to whole scan steps of 256 tiles, and 16 spare bytes
-struct MatchSelectLayout {
+struct TileCountLayout {
     uint64_t tiles;
     uint64_t tile_count;  // u32[tiles]
     uint64_t bytes;
-    static MatchSelectLayout from(uint64_t count) {
-        MatchSelectLayout w;
+    static TileCountLayout from(uint64_t count) {
+        TileCountLayout w;
         w.tiles = (count + 255u) / 256u;
         w.tile_count = 0;
         w.bytes = 4u * ((w.tiles + 255u) / 256u * 256u) + 16u;
+        return w;
+    }
+};
+
+// nexg_gather_plan_workspace and nexg_encap_plan_workspace (the two plans):
+// one u64 per 256-frame tile, rounded up the same way, and 16 spare bytes
+struct TileSumLayout {
+    uint64_t tiles;
+    uint64_t tile_sum;  // u64[tiles]
+    uint64_t bytes;
+    static TileSumLayout from(uint64_t count) {
+        TileSumLayout w;
+        w.tiles = (count + 255u) / 256u;
+        w.tile_sum = 0;
+        w.bytes = 8u * ((w.tiles + 255u) / 256u * 256u) + 16u;
         return w;
     }
 };

@@ -211,6 +211,28 @@ class Engine:
         """A workspace of at least `nbytes`, 8-B aligned."""
         return _torch().empty((nbytes + 7) // 8, dtype=_torch().int64, device=self.torch_device)
 
+    def _compact(self, fn, table: FrameBatch, hints, *, before, after=(), stream=None):
+        """What the three selects share. Calls
+
+            fn(ctx, *before, index, off, len, *after, count, workspace, workspace bytes, stream)
+
+        with fn one of nexg_decap_select, nexg_select_batch and
+        nexg_match_select, fresh (index, off, len) outputs for table.count
+        rows and a workspace of abi.select_workspace bytes (the one formula of
+        all three), then reads the selected count k back. Returns (index,
+        FrameBatch): the first k rows of the outputs over table.data, with
+        `hints`."""
+        torch = _torch()
+        count = table.count
+        idx, off, ln = self._table(count)
+        cnt = torch.zeros(1, dtype=torch.int64, device=self.torch_device)
+        ws_bytes = abi.select_workspace(count)
+        ws = self._workspace(ws_bytes)
+        self._check(fn(self.ctx, *before, _ptr(idx), _ptr(off), _ptr(ln), *after, _ptr(cnt), _ptr(ws), ws_bytes,
+                       self._stream(stream)))
+        k = int(cnt.item())  # waits for the kernels
+        return idx[:k], FrameBatch(data=table.data, count=k, offsets=off[:k], lengths=ln[:k], hints=hints)
+
     # --- hot path -------------------------------------------------------
     def parse(self, batch: FrameBatch, option: ParseOption = ParseOption(),
               mode: ParseMode = ParseMode.Lenient, out_kind: int = abi.OUT_DESC,
@@ -365,20 +387,11 @@ class Engine:
         {INNER_IPV4, INNER_IPV6} with ParseOption(from_ip_packet=True,
         offset=0) (see Engine.decap). Allocates the workspace and reads the
         selected count back: one synchronisation of the stream."""
-        torch = _torch()
         mask = 0
         for c in classes:
             mask |= 1 << int(c)
-        count = inner.count
-        idx, off, ln = self._table(count)
-        cnt = torch.zeros(1, dtype=torch.int64, device=self.torch_device)
-        ws_bytes = abi.decap_select_workspace(count)
-        ws = self._workspace(ws_bytes)
-        self._check(self.lib.nexg_decap_select(self.ctx, _ptr(tunnels), _ptr(inner.offsets), _ptr(inner.lengths), count,
-                                               mask, _ptr(idx), _ptr(off), _ptr(ln), _ptr(cnt), _ptr(ws), ws_bytes,
-                                               self._stream(stream)))
-        k = int(cnt.item())  # waits for the kernels
-        return idx[:k], FrameBatch(data=inner.data, count=k, offsets=off[:k], lengths=ln[:k], hints=inner.hints)
+        return self._compact(self.lib.nexg_decap_select, inner, inner.hints, stream=stream,
+                             before=(_ptr(tunnels), _ptr(inner.offsets), _ptr(inner.lengths), inner.count, mask))
 
     def select(self, batch: FrameBatch, records, flt, want_rule: bool = False, stream=None):
         """Order-preserving selection of frames by rule (nexg_select_batch;
@@ -405,20 +418,11 @@ class Engine:
         """
         torch = _torch()
         fc = flt.to_c()  # ValueError for what nexg_select_batch rejects
-        count = batch.count
-        dev = self.torch_device
-        idx, off, ln = self._table(count)
-        rule = torch.empty(max(count, 1), dtype=torch.uint8, device=dev) if want_rule else None
-        cnt = torch.zeros(1, dtype=torch.int64, device=dev)
-        ws_bytes = abi.select_workspace(count)
-        ws = self._workspace(ws_bytes)
-        self._check(self.lib.nexg_select_batch(self.ctx, _frames(batch), _ptr(records), ctypes.byref(fc), _ptr(idx),
-                                               _ptr(off), _ptr(ln), _ptr(rule), _ptr(cnt), _ptr(ws), ws_bytes,
-                                               self._stream(stream)))
-        k = int(cnt.item())  # waits for the kernels
-        sel = FrameBatch(data=batch.data, count=k, offsets=off[:k], lengths=ln[:k],
-                         hints=abi.FRAMES_MONOTONE if _ordered(batch) else 0)
-        return (idx[:k], sel, rule[:k]) if want_rule else (idx[:k], sel)
+        rule = torch.empty(max(batch.count, 1), dtype=torch.uint8, device=self.torch_device) if want_rule else None
+        idx, sel = self._compact(self.lib.nexg_select_batch, batch, abi.FRAMES_MONOTONE if _ordered(batch) else 0,
+                                 before=(_frames(batch), _ptr(records), ctypes.byref(fc)), after=(_ptr(rule),),
+                                 stream=stream)
+        return (idx, sel, rule[: sel.count]) if want_rule else (idx, sel)
 
     def match(self, batch: FrameBatch, records, pset, stream=None):
         """Fixed-string match on frame bytes (nexg_match_batch; an extension,
@@ -462,22 +466,11 @@ class Engine:
         selected frame, selected a FrameBatch (offsets + lengths) over the
         same data whose count is the selected count. Allocates the workspace
         and reads the selected count back: one synchronisation of the stream."""
-        torch = _torch()
         for name, v in (("any", any), ("all", all), ("none", none)):
             if not 0 <= int(v) <= 0xFFFFFFFF:
                 raise ValueError(f"{name} is a 32-bit mask")
-        count = batch.count
-        idx, off, ln = self._table(count)
-        cnt = torch.zeros(1, dtype=torch.int64, device=self.torch_device)
-        ws_bytes = abi.match_select_workspace(count)
-        ws = self._workspace(ws_bytes)
-        self._check(self.lib.nexg_match_select(self.ctx, _frames(batch), _ptr(matches), int(any), int(all), int(none),
-                                               _ptr(idx), _ptr(off), _ptr(ln), _ptr(cnt), _ptr(ws), ws_bytes,
-                                               self._stream(stream)))
-        k = int(cnt.item())  # waits for the kernels
-        sel = FrameBatch(data=batch.data, count=k, offsets=off[:k], lengths=ln[:k],
-                         hints=abi.FRAMES_MONOTONE if _ordered(batch) else 0)
-        return idx[:k], sel
+        return self._compact(self.lib.nexg_match_select, batch, abi.FRAMES_MONOTONE if _ordered(batch) else 0,
+                             before=(_frames(batch), _ptr(matches), int(any), int(all), int(none)), stream=stream)
 
     def gather(self, sel: FrameBatch, align: int = 1, stream=None):
         """Copy the frames of `sel` (usually Engine.select's table) into one

@@ -5,7 +5,7 @@
 // matching nexg_*_workspace returns; a region of u64 starts on 8 B and a region
 // of u32 on 4 B; the regions, each with the element count its kernels index
 // (stated here on its own: tiles of 1024 frames, chunks of 1024 counters, tiles
-// of 256 sorted positions), lie inside the workspace and do not overlap.
+// of 256 sorted positions or frames), lie inside the workspace and do not overlap.
 // Prints one line per failure and "ok <checks>" at the end; exit status 1 on any failure.
 #include <stdio.h>
 
@@ -77,6 +77,27 @@ int main() {
                   {{"totals", w.totals, 8, 2}, {"tile_bytes", w.tile_bytes, 8, tiles256}, {"mark", w.mark, 8, count},
                    {"tile_heads", w.tile_heads, 4, tiles256}, {"tile_brk", w.tile_brk, 4, tiles256},
                    {"starts", w.starts, 4, count}});
+        }
+        // the tile tables of the compactions and the plans: k_tile_scan touches
+        // `tiles` entries; the total goes to the caller's own slot, or (the
+        // fragment plan's frame total) to the first 8 spare bytes
+        for (uint64_t want : {nexg_select_workspace(count), nexg_decap_select_workspace(count),
+                              nexg_match_select_workspace(count)}) {
+            const nexg::TileCountLayout w = nexg::TileCountLayout::from(count);
+            expect(w.tiles == tiles256, "TileCountLayout", "tiles", count, 0);
+            check("TileCountLayout", count, 0, w.bytes, want, {{"tile_count", w.tile_count, 4, tiles256}});
+        }
+        for (uint64_t want : {nexg_gather_plan_workspace(count), nexg_encap_plan_workspace(count)}) {
+            const nexg::TileSumLayout w = nexg::TileSumLayout::from(count);
+            expect(w.tiles == tiles256, "TileSumLayout", "tiles", count, 0);
+            check("TileSumLayout", count, 0, w.bytes, want, {{"tile_sum", w.tile_sum, 8, tiles256}});
+        }
+        {
+            const nexg::FragPlanLayout w = nexg::FragPlanLayout::from(count);
+            expect(w.tiles == tiles256, "FragPlanLayout", "tiles", count, 0);
+            check("FragPlanLayout", count, 0, w.bytes, nexg_fragment_plan_workspace(count),
+                  {{"tile_frames", w.tile_frames, 8, tiles256}, {"tile_bytes", w.tile_bytes, 8, tiles256},
+                   {"frames_total", w.frames_total, 8, 1}});
         }
     }
     printf("ok %llu\n", (unsigned long long)checks);
