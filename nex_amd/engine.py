@@ -2,9 +2,13 @@
 
 torch is used only as device-memory / stream plumbing: frames, offsets and
 outputs are torch CUDA(HIP) tensors whose data pointers go straight to
-libnexg.so, and work is enqueued on torch's current stream.
+libnexg.so, and work is enqueued on torch's current stream, or on the
+`stream` a pass is given: its kernels, allocations and read-backs alike.
 """
+import contextlib
 import ctypes
+import functools
+import inspect
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
@@ -24,6 +28,26 @@ class NexgError(RuntimeError):
 def _torch():
     import torch
     return torch
+
+
+_CURRENT = contextlib.nullcontext()  # stateless, so one serves every call
+
+
+def _on_stream(fn):
+    """Run a method that takes `stream` under Engine._on(stream): what its
+    body allocates, fills, reduces and reads back through torch is then in
+    `stream`'s order and from its allocator pool, like the kernels it
+    enqueues there. With stream=None the method is called as it stands."""
+    at = list(inspect.signature(fn).parameters).index("stream") - 1  # in *args, which leaves self out
+
+    @functools.wraps(fn)
+    def method(self, *args, **kwargs):
+        stream = args[at] if len(args) > at else kwargs.get("stream")
+        if stream is None:
+            return fn(self, *args, **kwargs)
+        with self._on(stream):
+            return fn(self, *args, **kwargs)
+    return method
 
 
 def u32_tensor(values, device="cuda"):
@@ -196,6 +220,14 @@ class Engine:
         s = stream if stream is not None else torch.cuda.current_stream(self.torch_device)
         return ctypes.c_void_p(s.cuda_stream)
 
+    def _on(self, stream):
+        """The context a pass's host side runs in: torch.cuda.stream(stream),
+        or nothing to enter when `stream` is None or already current."""
+        torch = _torch()
+        if stream is None or stream == torch.cuda.current_stream(self.torch_device):
+            return _CURRENT
+        return torch.cuda.stream(stream)
+
     def _check(self, rc):
         if rc != abi.OK:
             raise NexgError(rc, self.lib.nexg_ctx_last_error(self.ctx).decode())
@@ -211,6 +243,7 @@ class Engine:
         """A workspace of at least `nbytes`, 8-B aligned."""
         return _torch().empty((nbytes + 7) // 8, dtype=_torch().int64, device=self.torch_device)
 
+    @_on_stream
     def _compact(self, fn, table: FrameBatch, hints, *, before, after=(), stream=None):
         """What the three selects share. Calls
 
@@ -234,6 +267,7 @@ class Engine:
         return idx[:k], FrameBatch(data=table.data, count=k, offsets=off[:k], lengths=ln[:k], hints=hints)
 
     # --- hot path -------------------------------------------------------
+    @_on_stream
     def parse(self, batch: FrameBatch, option: ParseOption = ParseOption(),
               mode: ParseMode = ParseMode.Lenient, out_kind: int = abi.OUT_DESC,
               out=None, stream=None):
@@ -280,6 +314,7 @@ class Engine:
               abi.OUT_VERDICT: abi.VERDICT_DTYPE}[out_kind]
         return out.cpu().numpy()[: batch.count * dt.itemsize].view(dt)
 
+    @_on_stream
     def sparse_expand(self, batch: FrameBatch, sparse, option: ParseOption = ParseOption(),
                       mode: ParseMode = ParseMode.Lenient, out=None, stream=None, grouped=False):
         """nexg_desc[count] (uint8 device tensor) from a NEXG_OUT_SPARSE output
@@ -293,6 +328,7 @@ class Engine:
         self._check(fn(self.ctx, _frames(batch), ctypes.byref(opt), _ptr(sparse), _ptr(out), self._stream(stream)))
         return out
 
+    @_on_stream
     def recompute_checksums(self, batch: FrameBatch, which: int = abi.FIX_IP | abi.FIX_L4,
                             option: ParseOption = ParseOption(), report=True, stream=None):
         """In-place checksum fix-up of batch.data with the mutable views'
@@ -306,6 +342,7 @@ class Engine:
                                                             _ptr(out), self._stream(stream)))
         return out
 
+    @_on_stream
     def rewrite(self, batch: FrameBatch, actions, index=None, option: ParseOption = ParseOption(), report=True,
                 stream=None):
         """Header fields rewritten in place in batch.data (nexg_rewrite_batch):
@@ -333,6 +370,7 @@ class Engine:
                                                 _ptr(index), _ptr(out), self._stream(stream)))
         return out[: batch.count * 8] if report else None
 
+    @_on_stream
     def decode_options(self, batch: FrameBatch, records, stream=None):
         """Ipv4Header.options / TcpHeader.options of every frame as positions
         (nexg_decode_options; ipv4.rs:442-508, tcp.rs:767-818). `records` is
@@ -343,6 +381,7 @@ class Engine:
                                                  self._stream(stream)))
         return out
 
+    @_on_stream
     def decap(self, batch: FrameBatch, records, which: int = abi.DECAP_VXLAN | abi.DECAP_GRE,
               vxlan_port: int = abi.VXLAN_PORT, stream=None):
         """Locate every VXLAN / GRE tunnel's inner frame inside `batch`
@@ -377,6 +416,7 @@ class Engine:
                            hints=abi.FRAMES_MONOTONE if _ordered(batch) else 0)
         return tunnels[: batch.count * 16], inner
 
+    @_on_stream
     def decap_select(self, tunnels, inner: FrameBatch, classes, stream=None):
         """Order-preserving compaction of a decap result (nexg_decap_select):
         the accepted tunnels whose inner class (abi.INNER_*) is in `classes`.
@@ -393,6 +433,7 @@ class Engine:
         return self._compact(self.lib.nexg_decap_select, inner, inner.hints, stream=stream,
                              before=(_ptr(tunnels), _ptr(inner.offsets), _ptr(inner.lengths), inner.count, mask))
 
+    @_on_stream
     def select(self, batch: FrameBatch, records, flt, want_rule: bool = False, stream=None):
         """Order-preserving selection of frames by rule (nexg_select_batch;
         an extension, the reference has no filter). `records` is the uint8
@@ -424,6 +465,7 @@ class Engine:
                                  stream=stream)
         return (idx, sel, rule[: sel.count]) if want_rule else (idx, sel)
 
+    @_on_stream
     def match(self, batch: FrameBatch, records, pset, stream=None):
         """Fixed-string match on frame bytes (nexg_match_batch; an extension,
         the reference has no payload search): which of up to 32 patterns of
@@ -455,6 +497,7 @@ class Engine:
                                               self._stream(stream)))
         return out[: batch.count * 8]
 
+    @_on_stream
     def match_select(self, batch: FrameBatch, matches, any: int = 0, all: int = 0, none: int = 0,  # noqa: A002
                      stream=None):
         """Order-preserving selection by Engine.match's rows
@@ -472,6 +515,7 @@ class Engine:
         return self._compact(self.lib.nexg_match_select, batch, abi.FRAMES_MONOTONE if _ordered(batch) else 0,
                              before=(_frames(batch), _ptr(matches), int(any), int(all), int(none)), stream=stream)
 
+    @_on_stream
     def gather(self, sel: FrameBatch, align: int = 1, stream=None):
         """Copy the frames of `sel` (usually Engine.select's table) into one
         dense buffer (nexg_gather_plan + nexg_gather_frames). Returns a new
@@ -498,6 +542,7 @@ class Engine:
         return FrameBatch(data=data[:total], count=n, offsets=offs, lengths=None if ln is None else ln[:n],
                           hints=0 if ln is None else abi.FRAMES_MONOTONE)
 
+    @_on_stream
     def encap(self, batch: FrameBatch, tunnels, index=None, flows=None, align: int = 1, report=True, stream=None):
         """Every frame of `batch` copied into a new buffer behind an outer
         Ethernet / IP / UDP + VXLAN or GRE header (nexg_encap_plan +
@@ -553,6 +598,7 @@ class Engine:
                          hints=0 if ln is None else abi.FRAMES_MONOTONE)
         return out, (rows[: n * 8] if report else None)
 
+    @_on_stream
     def fragment(self, batch: FrameBatch, mtu: int, ignore_df: bool = False, align: int = 1, report=True, stream=None):
         """Every IPv4 frame of `batch` whose total length exceeds `mtu` (68 to
         65535) cut into RFC 791 fragments, every other frame copied unchanged
@@ -606,6 +652,7 @@ class Engine:
                          hints=0 if align == 1 else abi.FRAMES_MONOTONE)
         return out, src[:k], (rows[: n * 16] if report else None)
 
+    @_on_stream
     def gather_rows(self, rows, row_bytes: int, index, stream=None):
         """Compact per-frame rows by a selected index (nexg_gather_rows):
         row k of the result is rows[index[k]], zeros where index[k] is past
@@ -623,6 +670,7 @@ class Engine:
                                               self._stream(stream)))
         return out[: n * row_bytes]
 
+    @_on_stream
     def flow(self, batch: FrameBatch, records, option=None, stream=None):
         """A flow row per frame (nexg_flow_batch; an extension, the reference
         has no flow notion): the Toeplitz RSS hash of the frame's addresses
@@ -652,6 +700,7 @@ class Engine:
                                              self._stream(stream)))
         return out[: batch.count * 8]
 
+    @_on_stream
     def flow_partition(self, batch: FrameBatch, flows, buckets: int, stream=None):
         """Stable split of `batch` into `buckets` (1..256) buckets by
         flows[i].hash % buckets (nexg_flow_partition): every flow lands whole
@@ -694,6 +743,7 @@ class Engine:
         return FrameBatch(data=table.data, count=hi - lo, offsets=table.offsets[lo:hi], lengths=table.lengths[lo:hi],
                           hints=table.bucket_hints | table.hints)
 
+    @_on_stream
     def flow_sort(self, flows, stream=None):
         """The frame numbers of a batch ordered by (flows[i].hash ascending,
         frame number ascending) (nexg_flow_sort): a stable radix sort on the
@@ -710,6 +760,7 @@ class Engine:
                                             self._stream(stream)))
         return idx[:count]
 
+    @_on_stream
     def flow_groups(self, batch: FrameBatch, records, flows, option=None, order=None, groups_cap=None, stream=None):
         """Per-flow counters of a batch (nexg_flow_groups): one row per run of
         equal hashes in the sorted order, with its packets, its bytes, its
@@ -766,6 +817,7 @@ class Engine:
             run(groups, n, None)
         return groups[: n * 32], group_of[:count], n, order
 
+    @_on_stream
     def flow_table_merge(self, batch: FrameBatch, records, groups, table=None, epoch=0, min_epoch=0, option=None,
                          table_cap=None, out=None, stream=None):
         """Merge one batch's groups into a flow table (nexg_flow_table_merge):
@@ -810,6 +862,7 @@ class Engine:
         n_out = int(cnt.item())  # waits for the kernels
         return out[: min(n_out, cap) * 64], n_out, slot[:n_groups]
 
+    @_on_stream
     def dns(self, batch: FrameBatch, records, port: int = abi.DNS_PORT, any_udp: bool = False, entries_cap=None,
             stream=None):
         """Walk every DNS message of `batch` in place (nexg_dns_batch +
@@ -848,6 +901,7 @@ class Engine:
         self._check(self.lib.nexg_dns_entries(self.ctx, fr, _ptr(out), _ptr(tile_first), _ptr(entries), cap, s))
         return out[: n * 32], tile_first, entries[: cap * 16], total
 
+    @_on_stream
     def probe_stream(self, data, write8, out=None, stream=None):
         """Calibration stream over a uint8 device tensor (nexg_probe_stream):
         the parse kernels' load shape, read-only or with the 8-B-per-64-B
@@ -862,6 +916,7 @@ class Engine:
                                                _ptr(out), self._stream(stream)))
         return out
 
+    @_on_stream
     def probe_write(self, out, stream=None):
         """Write-only calibration stream (nexg_probe_stream, out_per_64 = 64):
         the builders' copy-out shape over a uint8 device tensor (whole 16-KiB
@@ -870,6 +925,7 @@ class Engine:
         self._check(self.lib.nexg_probe_stream(self.ctx, None, nbytes, 64, _ptr(out), self._stream(stream)))
         return out
 
+    @_on_stream
     def probe_span_clock(self, batch: FrameBatch, option: ParseOption = ParseOption(),
                          mode: ParseMode = ParseMode.Lenient, out=None, stream=None):
         """One stamped launch of the span kernel over `batch`
@@ -888,6 +944,7 @@ class Engine:
                                                    _ptr(stamps), self._stream(stream)))
         return out, stamps
 
+    @_on_stream
     def probe_latency(self, buf, steps: int = 2000, start: int = 0, loaded: bool = False, stream=None):
         """Dependent HBM load latency (nexg_probe_latency; calibration, not a
         reference entry point) over a uint8 device scratch tensor (>= 4 MiB):
@@ -901,6 +958,7 @@ class Engine:
         cyc, ticks = (int(v) for v in out[:2].cpu())
         return ticks * 10.0 / steps, cyc / steps
 
+    @_on_stream
     def checksum(self, batch: FrameBatch, skipword: int, stream=None):
         """util::checksum(buf, skipword) per buffer (util.rs:65)."""
         torch = _torch()
@@ -933,6 +991,7 @@ class Engine:
             raise ValueError(f"out holds {out.numel() * out.element_size()} B; {count} frames of stride "
                              f"{stride} need {count * stride} B")
 
+    @_on_stream
     def build_udp4(self, src_ip, dst_ip, src_port=None, dst_port=None, ip_id=None,
                    def_src_port=0, def_dst_port=0, def_ip_id=0,
                    src_mac=b"\0" * 6, dst_mac=b"\0" * 6, ttl=64, ip_flags=0, dscp_ecn=0,
@@ -978,6 +1037,7 @@ class Engine:
         return torch.stack([src_ip.to(torch.int32), dst_ip.to(torch.int32),
                             lo16(src_port) | (lo16(dst_port) << 16), lo16(ip_id)], dim=1).contiguous()
 
+    @_on_stream
     def build_udp4_tuples(self, tuples, src_mac=b"\0" * 6, dst_mac=b"\0" * 6, ttl=64, ip_flags=0, dscp_ecn=0,
                           payload=None, out_stride=None, out=None, stream=None):
         """build_udp4 with each frame's tuple as one 16-B record
@@ -1000,6 +1060,7 @@ class Engine:
                                                     self._stream(stream)))
         return out
 
+    @_on_stream
     def build_udp6(self, src_ip, dst_ip, src_port=None, dst_port=None, def_src_port=0,
                    def_dst_port=0, src_mac=b"\0" * 6, dst_mac=b"\0" * 6, hop_limit=64,
                    traffic_class=0, flow_label=0, payload=None, out_stride=None, out=None,
@@ -1051,6 +1112,7 @@ class Engine:
         ip.ttl, ip.ip_flags, ip.tos = ttl, ip_flags, tos
         return ip
 
+    @_on_stream
     def build_tcp(self, family, src_ip, dst_ip, src_port=None, dst_port=None, seq=None, ack=None,
                   def_src_port=0, def_dst_port=0, def_seq=0, def_ack=0, flags=0, window=0xFFFF,
                   urgent_ptr=0, options=b"", payload=None, ip_id=None, def_ip_id=0,
@@ -1092,6 +1154,7 @@ class Engine:
                                                   self._stream(stream)))
         return out
 
+    @_on_stream
     def build_icmp_echo(self, family, src_ip, dst_ip, identifier=None, sequence=None,
                         def_identifier=0, def_sequence=0, icmp_type=None, icmp_code=0, payload=None,
                         ip_id=None, def_ip_id=0, src_mac=b"\0" * 6, dst_mac=b"\0" * 6, ttl=64,
@@ -1126,6 +1189,7 @@ class Engine:
         return out
 
     # --- synthetic workloads ----------------------------------------------
+    @_on_stream
     def build_arp(self, target_ip, sender_ip=None, def_sender_ip=b"\0" * 4, sender_mac=None,
                   def_sender_mac=b"\0" * 6, target_mac=None, def_target_mac=b"\0" * 6, eth_dst=None,
                   def_eth_dst=b"\xff" * 6, hardware_type=1, protocol_type=0x0800, operation=1,
@@ -1155,6 +1219,7 @@ class Engine:
                                                   self._stream(stream)))
         return out
 
+    @_on_stream
     def build_ndp_ns(self, src_ip, target_ip, src_mac=b"\0" * 6, dst_mac=None, hop_limit=255, tos=0,
                      flow_label=0, out_stride=86, out=None, stream=None):
         """examples/ndp.rs:82-108: NdpPacketBuilder::new(src_mac, src_ip,
@@ -1175,6 +1240,7 @@ class Engine:
                                                      self._stream(stream)))
         return out
 
+    @_on_stream
     def gen_batch(self, workload: int, count: int, seed: int = abi.DEFAULT_SEED,
                   first_index: int = 0, stream=None, record_gap: int = 0) -> FrameBatch:
         """Device-generated SURVEY.md App. C workload (UDP64: fixed 64-B
@@ -1209,6 +1275,7 @@ class Engine:
                               lengths=lengths, hints=abi.FRAMES_MONOTONE)
         return FrameBatch(data=data, count=count, offsets=offsets)
 
+    @_on_stream
     def gen_udp4_params(self, count, seed=abi.DEFAULT_SEED, first_index=0, stream=None):
         torch = _torch()
         dev = self.torch_device
@@ -1253,18 +1320,19 @@ class FlowTable:
         table position of every group's entry and the group of every frame,
         so frame i's entry is row slot[group_of[i]] of the new table."""
         eng = self.engine
-        flows = eng.flow(batch, records, self.option, stream)
-        groups, group_of, _, _ = eng.flow_groups(batch, records, flows, self.option, stream=stream)
-        table = self._cur[: self.count * 64]
-        while True:
-            if self._next.numel() < self.capacity * 64:
-                self._next = self._buffer()
-            _, n_out, slot = eng.flow_table_merge(batch, records, groups, table, epoch, min_epoch, self.option,
-                                                  table_cap=self.capacity, out=self._next, stream=stream)
-            if n_out <= self.capacity:
-                break
-            while self.capacity < n_out:
-                self.capacity *= 2
+        with eng._on(stream):  # the reallocation below follows `stream` too
+            flows = eng.flow(batch, records, self.option, stream)
+            groups, group_of, _, _ = eng.flow_groups(batch, records, flows, self.option, stream=stream)
+            table = self._cur[: self.count * 64]
+            while True:
+                if self._next.numel() < self.capacity * 64:
+                    self._next = self._buffer()
+                _, n_out, slot = eng.flow_table_merge(batch, records, groups, table, epoch, min_epoch, self.option,
+                                                      table_cap=self.capacity, out=self._next, stream=stream)
+                if n_out <= self.capacity:
+                    break
+                while self.capacity < n_out:
+                    self.capacity *= 2
         self._cur, self._next = self._next, self._cur
         self.count = n_out
         return slot, group_of
