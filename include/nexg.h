@@ -1634,6 +1634,161 @@ static inline uint64_t nexg_flow_table_workspace(uint64_t n_in, uint64_t n_group
     return 8u * n + 4u * ((tiles + 1u) & ~(uint64_t)1u);
 }
 
+/* ---- IPv4 reassembly (RFC 791 section 3.2's way back; extension) ------------------
+ * The inverse of nexg_fragment_*: the IPv4 fragments of a frame table are
+ * grouped into datagrams, and every datagram whose pieces are all in the table
+ * becomes one output frame. The first many-to-one pass: a group of input
+ * frames, found by sorting, becomes one output frame. The reference has no
+ * reassembly; this text is the whole specification, restated in plain Python
+ * by nex_amd.reassemble.reassemble_host. No records are needed: the rules read
+ * the frame's own bytes, as the fragment pass does.
+ *
+ * Per frame i, in this order:
+ *  1 extent   An extent that leaves [0, data_bytes) or a length above 65535: no
+ *             output, status NEXG_ERR_BAD_EXTENT, kind NEXG_REASM_NONE.
+ *  2 not IPv4 nexg_fragment_plan's rule 3: bytes 12..13 are not 0x0800, len < 34,
+ *             version != 4, IHL < 5, 14 + hl > len, TL < hl, or 14 + TL > len:
+ *             kind NEXG_REASM_PASS, one output frame, the whole input copied
+ *             unchanged. IPv6 and VLAN-tagged frames fall here.
+ *  3 whole    MF clear and fragment offset 0: NEXG_REASM_PASS (the bytes past
+ *             14 + TL are copied too).
+ *  4 fragment otherwise. fo is the 13-bit offset, mf the MF bit, d = TL - hl; the
+ *             key is (source address, destination address, protocol,
+ *             identification), compared exactly.
+ *
+ * Datagrams. The fragments of one key form a datagram; its members are ordered
+ * by (fo ascending, frame number ascending). It is complete when member 0 has
+ * fo == 0; for every k >= 1, 8 fo_k == 8 fo_(k-1) + d_(k-1) and d_(k-1) >= 8 (no
+ * gap, no overlap, no duplicate); MF is set on every member but the last and
+ * clear on the last, and the last has d >= 1; hl_0 + 8 fo_last + d_last <= 65535;
+ * and its hash run is not mixed (below).
+ *   complete   Member 0 is the head, kind NEXG_REASM_HEAD, the others are
+ *              NEXG_REASM_PART. One output frame stands at the head's place:
+ *              output frames are ordered by the input index of the PASS or
+ *              HEAD frame that produces them. Its length is 14 + hl_0 + D, D =
+ *              8 fo_last + d_last. Bytes 0..13 and the hl_0 header bytes come
+ *              from the head, options included; each member's data bytes
+ *              [14 + hl_k, 14 + hl_k + d_k) land at 14 + hl_0 + 8 fo_k. In the
+ *              header the total length is hl_0 + D, bytes 6..7 become old &
+ *              0xC000 (reserved and DF kept, MF cleared, offset 0) and the
+ *              checksum is recomputed as ipv4::checksum. Everything else in
+ *              the other members' Ethernet and IP headers is ignored, as are
+ *              input bytes past 14 + TL. Input header checksums are not
+ *              verified: select on NEXG_C_IP_OK first for that.
+ *   incomplete every member is NEXG_REASM_HELD, no output frame, status
+ *              NEXG_FRAME_OK: the bytes stay where they are for the caller to
+ *              carry into a later batch (nexg_reasm_held).
+ *
+ * Finding the groups. A 32-bit hash is taken over 12 key bytes: the source
+ * address, the destination address, then 0, the protocol, 0, 0 (the protocol
+ * where nexg_flow_batch has the source port, 0 for the destination port): the
+ * Toeplitz hash of nexg_flow_batch with NEXG_FLOW_DEFAULT_KEY. The
+ * identification is not hashed. The fragments are ordered by (hash,
+ * identification, fo, frame number) with nexg_flow_sort's stable radix passes:
+ * four 8-bit digit passes over id << 13 | fo, then four over the hash starting
+ * from that order. A run of equal (hash, identification) is one datagram
+ * unless two members' exact keys differ: such a run is mixed (a 32-bit hash
+ * collision between two address pairs that use one identification at once),
+ * every member of it is NEXG_REASM_HELD with flag NEXG_REASM_COLLISION and none
+ * is reassembled on the device; the caller resolves those few frames
+ * (reassemble_host does it exactly). Heads, breaks and contiguity are found
+ * per sorted position, a group's verdict by prefix differences: the work is
+ * linear in the count however the groups are sized. Deterministic, no atomics.
+ *
+ * Out of scope: IPv6 fragment headers; overlap or duplicate resolution (a
+ * retransmitted fragment makes its datagram HELD); resolving a mixed run on the
+ * device; verifying input checksums; fixing L4 checksums; VLAN-tagged or
+ * tunnelled inner headers; TCP stream reassembly; a hash table across batches
+ * (carrying over is done by re-submitting the held frames). */
+#define NEXG_REASM_NONE 0  /* no output frame: an error status */
+#define NEXG_REASM_PASS 1  /* one output frame, the input copied unchanged */
+#define NEXG_REASM_HEAD 2  /* member 0 of a complete datagram: its output frame stands here */
+#define NEXG_REASM_PART 3  /* another member of a complete datagram */
+#define NEXG_REASM_HELD 4  /* a fragment of an incomplete datagram or of a mixed run */
+#define NEXG_REASM_COLLISION 0x1u
+typedef struct nexg_reasm {        /* 16 bytes, one per input frame */
+    uint8_t status;                /* NEXG_FRAME_OK / NEXG_ERR_* */
+    uint8_t kind;                  /* NEXG_REASM_* */
+    uint8_t hdr_len;               /* hl of a fragment, else 0 */
+    uint8_t flags;                 /* NEXG_REASM_COLLISION */
+    uint16_t members;              /* HEAD: member count, else 0 */
+    uint16_t data_len;             /* HEAD: D, the datagram's data bytes, else 0 (what the fill's head
+                                      takes the total length, the checksum and out_len from) */
+    uint32_t out;                  /* PASS / HEAD / PART: index of the output frame it went into, else 0xFFFFFFFF */
+    uint32_t head;                 /* HEAD / PART: input index of the head, else 0xFFFFFFFF */
+} nexg_reasm;
+
+/* Classify, sort, group, then two scans. out_first[i] (count + 1 entries, 4-B
+ * aligned) = the number of output frames of the frames before i (each frame
+ * gives 0 or 1), out_bytes[i] (count + 1 entries, 8-B aligned) = the sum of
+ * their output frames' lengths, each rounded up to `align` (1, 4, 8 or 16);
+ * the totals are in the last entries. rows[i] (required, 16-B aligned) reports
+ * frame i. workspace: caller-owned device memory (16-B aligned) of at least the
+ * bytes the helper below gives (NEXG_EINVAL when smaller): nexg_flow_sort's
+ * workspace, then 32 B of classification, two sort keys, a mark, the order, an
+ * output length and a group start per frame, and four values per 256-frame
+ * tile. Scans only, no atomics. count == 0 writes the two zeros and launches
+ * nothing else. NEXG_EINVAL also for count > 2^32 - 1, a NULL or misaligned
+ * pointer, an align other than 1, 4, 8 or 16. 51 kernels on `stream`, 40 of them
+ * the eight radix passes. */
+int nexg_reasm_plan(nexg_ctx* ctx, const nexg_frames* frames, uint32_t align, uint32_t* out_first, uint64_t* out_bytes,
+                    nexg_reasm* rows, void* workspace, uint64_t workspace_bytes, void* stream);
+static inline uint64_t nexg_reasm_plan_workspace(uint64_t count) {
+    const uint64_t tiles = (count + 255u) / 256u;
+    const uint64_t even = (count + 1u) & ~(uint64_t)1u, even_tiles = (tiles + 1u) & ~(uint64_t)1u;
+    const uint64_t sort = (nexg_flow_sort_workspace(count) + 15u) & ~(uint64_t)15u;
+    return sort + 56u * count + 24u * tiles + 32u + 12u * even + 4u * even_tiles;
+}
+
+/* The fill. A PASS frame is copied to out_data (16-B aligned) + out_bytes[i];
+ * a HEAD writes its datagram's header (total length, flags / offset and
+ * checksum fixed) and its own data there; a PART copies its data to
+ * out_bytes[h] + 14 + rows[h].hdr_len + 8 fo with h = rows[i].head and fo, d
+ * from its own bytes; the member with MF clear writes the zero pad behind the
+ * datagram. For the output frame f = out_first[i] of a PASS or HEAD frame:
+ * out_offsets[f] (out_count + 1 entries, 8-B aligned) = where it starts,
+ * out_len[f] its length, out_src[f] = i (4-B aligned, out_count entries each),
+ * the index nexg_gather_rows takes to carry per-frame rows to the output;
+ * out_offsets[out_count] = out_bytes[count]. rows, out_first and out_bytes are
+ * caller memory: whatever they hold, no byte store lands at or past out_cap or
+ * outside [out_bytes[h], out_bytes[h + 1]) of the head h < count it names (h =
+ * i for PASS and HEAD), no table store lands at an index at or above
+ * min(out_first[i + 1], out_count), and every loop is bounded by the frame's
+ * own bytes. A rows[i].data_len that is not its datagram's D changes the
+ * total length (bytes 16..17) and the checksum (bytes 24..25) of that head's
+ * output header and its out_len, and nothing else: no bound depends on it.
+ * Pads are zero. With a consistent plan every byte of an output
+ * frame is written exactly once. The output is never read. Source reads follow
+ * the 16-B block rule. Deterministic, no atomics, no workspace. NEXG_EINVAL: an
+ * align other than 1, 4, 8 or 16, a NULL rows (count > 0), out_first, out_bytes
+ * or out_offsets, a NULL out_len or out_src with out_count > 0, a NULL
+ * out_data with out_cap > 0, a misaligned pointer, count or out_count > 2^32 -
+ * 1. count == 0 launches nothing but the copy of the total. With align 1,
+ * {out_data, total, out_offsets} is a packed batch that nexg_parse_batch,
+ * nexg_decap_batch and nexg_fragment_plan take as it stands; with a larger
+ * align, {out_data, total, out_offsets, out_len} an offsets + lengths batch
+ * (monotone). One kernel on `stream`. */
+int nexg_reasm_frames(nexg_ctx* ctx, const nexg_frames* frames, uint32_t align, const nexg_reasm* rows,
+                      const uint32_t* out_first, const uint64_t* out_bytes, uint64_t out_count, uint64_t* out_offsets,
+                      uint32_t* out_len, uint32_t* out_src, uint8_t* out_data, uint64_t out_cap, void* stream);
+
+/* The NEXG_REASM_HELD frames as a frame table, in order: nexg_select_batch's
+ * compaction with rows[i].kind == NEXG_REASM_HELD as the predicate. `count` is
+ * the number of rows and must be frames->count (NEXG_EINVAL otherwise).
+ * out_index[k] (4-B aligned) = the frame number, out_off[k] (8-B aligned) /
+ * out_len[k] its table entry, *out_count (device memory, 8-B aligned) the
+ * number held; the outputs hold `count` entries. workspace: caller-owned
+ * device memory (4-B aligned) of at least the bytes the helper below gives.
+ * The table goes to nexg_gather_plan / nexg_parse_batch as it stands. Three
+ * kernels on `stream`; count == 0 launches the scan alone. */
+int nexg_reasm_held(nexg_ctx* ctx, const nexg_frames* frames, const nexg_reasm* rows, uint64_t count,
+                    uint32_t* out_index, uint64_t* out_off, uint32_t* out_len, uint64_t* out_count, void* workspace,
+                    uint64_t workspace_bytes, void* stream);
+static inline uint64_t nexg_reasm_held_workspace(uint64_t count) {
+    const uint64_t tiles = (count + 255u) / 256u;
+    return 4u * ((tiles + 255u) / 256u * 256u) + 16u;
+}
+
 /* ---- calibration (not a reference entry point) ---------------------------
  * The HBM stream ceilings the parse kernels are measured against, on the
  * caller's own buffer and box: `bytes` (a multiple of 16384) read with the

@@ -46,6 +46,10 @@
  *                           RFC 791 fragmentation to an MTU: each piece the
  *                           bytes Ipv4PacketBuilder gives for its fields
  *                           (Ipv4Flags, fragment_offset, ipv4::checksum)
+ *   Engine::reassemble_plan / reassemble / reassemble_held / reassemble_bufs
+ *                           no reference counterpart: the way back, IPv4
+ *                           fragments sorted into datagrams, every complete
+ *                           one an output frame, the rest reported as held
  *   FlowOption, Engine::flow / flow_partition / flow_bufs
  *                           no reference counterpart (an extension): the
  *                           Toeplitz RSS hash of every frame's flow key and the
@@ -2341,6 +2345,103 @@ class Engine {  // one nexg context on one gfx950 device, one stream
             check_hip(hipMemcpyAsync(out.lengths.data(), d_len, t.frames * 4, hipMemcpyDeviceToHost, stream_), "D2H");
             check_hip(hipMemcpyAsync(out.src.data(), d_src, t.frames * 4, hipMemcpyDeviceToHost, stream_), "D2H");
         }
+        if (t.bytes) check_hip(hipMemcpyAsync(out.data.data(), d_data, t.bytes, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        return out;
+    }
+
+    // What reassemble will write (nexg_reasm_plan): out_first and out_bytes
+    // hold frames.count + 1 entries, rows frames.count. Returns the number
+    // of output frames and their bytes (one stream synchronisation) to
+    // allocate for reassemble. align: 1, 4, 8 or 16.
+    FragmentTotals reassemble_plan(const nexg_frames& frames, uint32_t align, uint32_t* out_first, uint64_t* out_bytes,
+                                   nexg_reasm* rows) {
+        DeviceScope ds(device_);
+        const uint64_t wsb = nexg_reasm_plan_workspace(frames.count);
+        void* ws = scratch(62, wsb);
+        check(nexg_reasm_plan(ctx_, &frames, align, out_first, out_bytes, rows, ws, wsb, stream_), "nexg_reasm_plan");
+        uint32_t n = 0;
+        FragmentTotals t{0, 0};
+        check_hip(hipMemcpyAsync(&n, out_first + frames.count, 4, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipMemcpyAsync(&t.bytes, out_bytes + frames.count, 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        t.frames = n;
+        return t;
+    }
+
+    // Every complete IPv4 datagram of the table as one frame at its head's
+    // place, every frame that is no fragment unchanged, at out_data +
+    // out_bytes[i] on, pads zero, nothing at or past out_cap
+    // (nexg_reasm_frames); out_offsets (out_count + 1 entries), out_len and
+    // out_src (out_count each) are the output frames' table and the head or
+    // pass-through input frame of each.
+    void reassemble(const nexg_frames& frames, uint32_t align, const nexg_reasm* rows, const uint32_t* out_first,
+                    const uint64_t* out_bytes, uint64_t out_count, uint64_t* out_offsets, uint32_t* out_len, uint32_t* out_src,
+                    uint8_t* out_data, uint64_t out_cap) {
+        DeviceScope ds(device_);
+        check(nexg_reasm_frames(ctx_, &frames, align, rows, out_first, out_bytes, out_count, out_offsets, out_len, out_src,
+                                out_data, out_cap, stream_),
+              "nexg_reasm_frames");
+    }
+
+    // The NEXG_REASM_HELD frames as a frame table over frames.data, in order
+    // (nexg_reasm_held); the outputs hold frames.count entries. Returns the
+    // number held (one stream synchronisation).
+    uint64_t reassemble_held(const nexg_frames& frames, const nexg_reasm* rows, uint32_t* out_index, uint64_t* out_off,
+                             uint32_t* out_len) {
+        DeviceScope ds(device_);
+        const uint64_t wsb = nexg_reasm_held_workspace(frames.count);
+        void* ws = scratch(63, wsb);
+        uint64_t* d_count = static_cast<uint64_t*>(scratch(64, 8));
+        check(nexg_reasm_held(ctx_, &frames, rows, frames.count, out_index, out_off, out_len, d_count, ws, wsb, stream_),
+              "nexg_reasm_held");
+        return read_u64(d_count);
+    }
+
+    // reassemble of host frames: output frame f lies in `data` at offsets[f],
+    // lengths[f] bytes, and its head or pass-through was input frame src[f];
+    // rows has one entry per input frame; held lists the input frames that
+    // wait for the rest of their datagram.
+    struct Reassembled {
+        std::vector<nexg_reasm> rows;
+        std::vector<uint64_t> offsets;  // lengths.size() + 1
+        std::vector<uint32_t> lengths, src, held;
+        std::vector<uint8_t> data;
+    };
+    Reassembled reassemble_bufs(const std::vector<std::vector<uint8_t>>& frames, uint32_t align = 1) {
+        DeviceScope ds(device_);
+        const uint64_t n = frames.size();
+        Reassembled out;
+        out.offsets.assign(1, 0);
+        if (align != 1 && align != 4 && align != 8 && align != 16) throw Error("reassemble: align must be 1, 4, 8 or 16");
+        if (n == 0) return out;
+        HostBatch hb(*this, frames);
+        uint32_t* d_first = static_cast<uint32_t*>(scratch(65, (n + 1) * 4));
+        uint64_t* d_bytes = static_cast<uint64_t*>(scratch(66, (n + 1) * 8));
+        nexg_reasm* d_rows = static_cast<nexg_reasm*>(scratch(67, n * sizeof(nexg_reasm)));
+        const FragmentTotals t = reassemble_plan(hb.fb, align, d_first, d_bytes, d_rows);
+        uint64_t* d_off = static_cast<uint64_t*>(scratch(68, (t.frames + 1) * 8));
+        uint32_t* d_len = static_cast<uint32_t*>(scratch(69, t.frames * 4));
+        uint32_t* d_src = static_cast<uint32_t*>(scratch(70, t.frames * 4));
+        uint8_t* d_data = static_cast<uint8_t*>(scratch(71, t.bytes));
+        reassemble(hb.fb, align, d_rows, d_first, d_bytes, t.frames, d_off, d_len, d_src, d_data, t.bytes);
+        uint32_t* h_index = static_cast<uint32_t*>(scratch(72, n * 4));
+        uint64_t* h_off = static_cast<uint64_t*>(scratch(73, n * 8));
+        uint32_t* h_len = static_cast<uint32_t*>(scratch(74, n * 4));
+        const uint64_t held = reassemble_held(hb.fb, d_rows, h_index, h_off, h_len);
+        out.rows.resize(n);
+        out.offsets.resize(t.frames + 1);
+        out.lengths.resize(t.frames);
+        out.src.resize(t.frames);
+        out.held.resize(held);
+        out.data.resize(t.bytes);
+        check_hip(hipMemcpyAsync(out.rows.data(), d_rows, n * sizeof(nexg_reasm), hipMemcpyDeviceToHost, stream_), "D2H");
+        check_hip(hipMemcpyAsync(out.offsets.data(), d_off, (t.frames + 1) * 8, hipMemcpyDeviceToHost, stream_), "D2H");
+        if (t.frames) {
+            check_hip(hipMemcpyAsync(out.lengths.data(), d_len, t.frames * 4, hipMemcpyDeviceToHost, stream_), "D2H");
+            check_hip(hipMemcpyAsync(out.src.data(), d_src, t.frames * 4, hipMemcpyDeviceToHost, stream_), "D2H");
+        }
+        if (held) check_hip(hipMemcpyAsync(out.held.data(), h_index, held * 4, hipMemcpyDeviceToHost, stream_), "D2H");
         if (t.bytes) check_hip(hipMemcpyAsync(out.data.data(), d_data, t.bytes, hipMemcpyDeviceToHost, stream_), "D2H");
         check_hip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
         return out;

@@ -72,6 +72,9 @@ def load():
         "nexg_fragment_plan": (I, [P, ctypes.POINTER(abi.Frames), ctypes.POINTER(abi.FragOptionC), P, P, P, P, U64, P]),
         "nexg_fragment_frames": (I, [P, ctypes.POINTER(abi.Frames), ctypes.POINTER(abi.FragOptionC), P, P, U64, P, P, P, P,
                                      U64, P]),
+        "nexg_reasm_plan": (I, [P, ctypes.POINTER(abi.Frames), U32, P, P, P, P, U64, P]),
+        "nexg_reasm_frames": (I, [P, ctypes.POINTER(abi.Frames), U32, P, P, P, U64, P, P, P, P, U64, P]),
+        "nexg_reasm_held": (I, [P, ctypes.POINTER(abi.Frames), P, U64, P, P, P, P, P, U64, P]),
         "nexg_flow_batch": (I, [P, ctypes.POINTER(abi.Frames), P, ctypes.POINTER(abi.FlowOptionC), P, P]),
         "nexg_flow_partition": (I, [P, ctypes.POINTER(abi.Frames), P, U32, P, P, P, P, P, U64, P]),
         "nexg_flow_sort": (I, [P, P, U64, P, P, U64, P]),

@@ -660,12 +660,37 @@ def flow_table_workspace(n_in, n_groups):
     return 8 * n + 4 * ((tiles + 1) & ~1)
 
 
+# IPv4 reassembly (nexg_reasm_plan / nexg_reasm_frames / nexg_reasm_held; an
+# extension: the reference has no reassembly)
+REASM_NONE, REASM_PASS, REASM_HEAD, REASM_PART, REASM_HELD = 0, 1, 2, 3, 4
+REASM_COLLISION = 0x1
+REASM_NO_INDEX = 0xFFFFFFFF  # nexg_reasm.out / .head of a frame that has none
+REASM_DTYPE = np.dtype([("status", "u1"), ("kind", "u1"), ("hdr_len", "u1"), ("flags", "u1"), ("members", "<u2"),
+                        ("data_len", "<u2"), ("out", "<u4"), ("head", "<u4")])
+assert REASM_DTYPE.itemsize == 16
+
+
+def reasm_plan_workspace(count):
+    """nexg_reasm_plan_workspace: bytes of nexg_reasm_plan's workspace."""
+    count = int(count)
+    tiles = (count + 255) // 256
+    even, even_tiles = (count + 1) & ~1, (tiles + 1) & ~1
+    sort = (flow_sort_workspace(count) + 15) & ~15
+    return sort + 56 * count + 24 * tiles + 32 + 12 * even + 4 * even_tiles
+
+
+def reasm_held_workspace(count):
+    """nexg_reasm_held_workspace: bytes of nexg_reasm_held's workspace."""
+    return select_workspace(count)
+
+
 #: static inline helpers of include/nexg.h (header-only, not exported)
 HEADER_INLINE = ("nexg_sparse_decode", "nexg_grouped_code", "nexg_grouped_exc_slot", "nexg_offsets32_bases",
                  "nexg_offsets32_bytes", "nexg_decap_select_workspace", "nexg_dns_tile_first_bytes",
                  "nexg_select_workspace", "nexg_match_select_workspace", "nexg_gather_plan_workspace", "nexg_encap_plan_workspace",
                  "nexg_fragment_plan_workspace", "nexg_flow_partition_workspace",
-                 "nexg_flow_sort_workspace", "nexg_flow_groups_workspace", "nexg_flow_table_workspace")
+                 "nexg_flow_sort_workspace", "nexg_flow_groups_workspace", "nexg_flow_table_workspace",
+                 "nexg_reasm_plan_workspace", "nexg_reasm_held_workspace")
 
 #: every symbol include/nexg.h declares (tests check the .so exports them)
 EXPORTED_SYMBOLS = (
@@ -679,6 +704,7 @@ EXPORTED_SYMBOLS = (
     "nexg_frag_option_check", "nexg_fragment_plan", "nexg_fragment_frames",
     "nexg_flow_batch", "nexg_flow_partition", "nexg_flow_sort", "nexg_flow_groups",
     "nexg_flow_table_merge",
+    "nexg_reasm_plan", "nexg_reasm_frames", "nexg_reasm_held",
     "nexg_probe_span_clock", "nexg_probe_latency",
     "nexg_sparse_expand", "nexg_grouped_expand", "nexg_recompute_checksums_batch",
     "nexg_rx_config_default", "nexg_rx_open", "nexg_rx_next_batch", "nexg_rx_stats", "nexg_rx_close",

@@ -574,6 +574,63 @@ int nexg_fragment_frames(nexg_ctx* ctx, const nexg_frames* frames, const nexg_fr
                                                       as_stream(stream)));
 }
 
+int nexg_reasm_plan(nexg_ctx* ctx, const nexg_frames* frames, uint32_t align, uint32_t* out_first, uint64_t* out_bytes,
+                    nexg_reasm* rows, void* workspace, uint64_t workspace_bytes, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    if (align != 1 && align != 4 && align != 8 && align != 16)
+        return fail(ctx, NEXG_EINVAL, "reasm_plan: align must be 1, 4, 8 or 16%s", nullptr);
+    const uint64_t count = frames->count;
+    if (int rc = check_count(ctx, "reasm_plan", count)) return rc;
+    if (!out_first || !out_bytes) return fail(ctx, NEXG_EINVAL, "NULL out_first or out_bytes%s", nullptr);
+    if (count && (!rows || !workspace)) return fail(ctx, NEXG_EINVAL, "NULL rows or workspace%s", nullptr);
+    if (int rc = check_workspace(ctx, "reasm_plan", count, workspace_bytes, nexg_reasm_plan_workspace(count))) return rc;
+    if (misaligned(7u, out_bytes) || misaligned(3u, out_first) || misaligned(15u, rows, workspace))
+        return fail(ctx, NEXG_EINVAL, "misaligned output, rows or workspace%s", nullptr);
+    const nexg::ParseArgs a = to_args(frames);
+    DeviceGuard g(ctx);
+    return launched(ctx, nexg::launch_reasm_plan(a, align, out_first, out_bytes, rows, workspace, as_stream(stream)));
+}
+
+int nexg_reasm_frames(nexg_ctx* ctx, const nexg_frames* frames, uint32_t align, const nexg_reasm* rows,
+                      const uint32_t* out_first, const uint64_t* out_bytes, uint64_t out_count, uint64_t* out_offsets,
+                      uint32_t* out_len, uint32_t* out_src, uint8_t* out_data, uint64_t out_cap, void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    if (align != 1 && align != 4 && align != 8 && align != 16)
+        return fail(ctx, NEXG_EINVAL, "reasm_frames: align must be 1, 4, 8 or 16%s", nullptr);
+    if (int rc = check_count(ctx, "reasm_frames", frames->count)) return rc;
+    if (out_count > 0xFFFFFFFFull) return fail(ctx, NEXG_EINVAL, "reasm_frames: more than 2^32 - 1 output frames%s", nullptr);
+    if (!out_first || !out_bytes || !out_offsets) return fail(ctx, NEXG_EINVAL, "NULL out_first, out_bytes or out_offsets%s", nullptr);
+    if (frames->count && !rows) return fail(ctx, NEXG_EINVAL, "NULL rows%s", nullptr);
+    if (out_count && (!out_len || !out_src)) return fail(ctx, NEXG_EINVAL, "NULL out_len or out_src%s", nullptr);
+    if (out_cap && !out_data) return fail(ctx, NEXG_EINVAL, "NULL out_data with a nonzero capacity%s", nullptr);
+    if (misaligned(7u, out_bytes, out_offsets) || misaligned(3u, out_first, out_len, out_src) || misaligned(15u, out_data, rows))
+        return fail(ctx, NEXG_EINVAL, "misaligned rows, out_first, out_bytes, table or out_data%s", nullptr);
+    const nexg::ParseArgs a = to_args(frames);
+    DeviceGuard g(ctx);
+    return launched(ctx, nexg::launch_reasm_frames(a, align, rows, out_first, out_bytes, out_count, out_offsets, out_len,
+                                                   out_src, out_data, out_cap, as_stream(stream)));
+}
+
+int nexg_reasm_held(nexg_ctx* ctx, const nexg_frames* frames, const nexg_reasm* rows, uint64_t count, uint32_t* out_index,
+                    uint64_t* out_off, uint32_t* out_len, uint64_t* out_count, void* workspace, uint64_t workspace_bytes,
+                    void* stream) {
+    if (!ctx) return NEXG_EINVAL;
+    if (!frames_valid(frames)) return fail(ctx, NEXG_EINVAL, "invalid frame batch%s", nullptr);
+    if (count != frames->count) return fail(ctx, NEXG_EINVAL, "reasm_held: count is not the table's%s", nullptr);
+    if (int rc = check_count(ctx, "reasm_held", count)) return rc;
+    if (!out_count) return fail(ctx, NEXG_EINVAL, "NULL out_count%s", nullptr);
+    if (count && (!rows || !out_index || !out_off || !out_len || !workspace))
+        return fail(ctx, NEXG_EINVAL, "NULL rows, output or workspace%s", nullptr);
+    if (int rc = check_workspace(ctx, "reasm_held", count, workspace_bytes, nexg_reasm_held_workspace(count))) return rc;
+    if (misaligned(15u, rows) || misaligned(7u, out_off, out_count) || misaligned(3u, out_index, out_len, workspace))
+        return fail(ctx, NEXG_EINVAL, "misaligned rows, output or workspace%s", nullptr);
+    const nexg::ParseArgs a = to_args(frames);
+    DeviceGuard g(ctx);
+    return launched(ctx, nexg::launch_reasm_held(a, rows, out_index, out_off, out_len, out_count, workspace, as_stream(stream)));
+}
+
 int nexg_gather_rows(nexg_ctx* ctx, const void* rows, uint32_t row_bytes, uint64_t rows_count,
                      const uint32_t* index, uint64_t n, void* out, void* stream) {
     if (!ctx) return NEXG_EINVAL;

@@ -375,28 +375,39 @@ hipError_t launch_flow_partition(const ParseArgs& a, const nexg_flow* flows, uin
 // alone. The workspace is the partition's at 256 buckets, then two buffers of
 // `count` pairs (nexg_flow_sort_workspace).
 
-template <bool kFirst>
+// kOrdered (with kFirst): the chain starts from the order a chain before it
+// left, not from the table's: position k holds frame order[k] (an entry past
+// the table stands for key 0), which is how a sort by two keys is two chains.
+template <bool kFirst, bool kOrdered = false>
 struct SortDigit {
-    const void* src;  // kFirst: the flow rows; else the pairs the pass before stored
+    const void* src;  // kFirst: the rows, the key their low word; else the pairs the pass before stored
+    const uint32_t* order;  // kOrdered only
+    uint64_t count;
     uint32_t shift;
     __device__ __forceinline__ uint64_t pair(uint64_t idx) const {
-        const uint64_t v = NEXG_GLOBAL(uint64_t, src)[idx];
-        return kFirst ? (v & 0xFFFFFFFFull) | idx << 32 : v;
+        if constexpr (kFirst && kOrdered) {
+            const uint64_t i = order[idx];
+            const uint64_t v = i < count ? NEXG_GLOBAL(uint64_t, src)[i] : 0ull;
+            return (v & 0xFFFFFFFFull) | i << 32;
+        } else {
+            const uint64_t v = NEXG_GLOBAL(uint64_t, src)[idx];
+            return kFirst ? (v & 0xFFFFFFFFull) | idx << 32 : v;
+        }
     }
     __device__ __forceinline__ uint32_t operator()(uint64_t idx) const { return ((uint32_t)pair(idx) >> shift) & 255u; }
 };
 
 // k_part_count with the pass's digit as the bucket
-template <bool kFirst>
-__global__ __launch_bounds__(256) void k_sort_count(const void* src, uint64_t count, uint32_t shift, uint64_t T,
-                                                    uint32_t* hist) {
+template <bool kFirst, bool kOrdered = false>
+__global__ __launch_bounds__(256) void k_sort_count(const void* src, const uint32_t* order, uint64_t count, uint32_t shift,
+                                                    uint64_t T, uint32_t* hist) {
     __shared__ uint32_t s_w[4][256];
     const uint32_t t = threadIdx.x, wv = t >> 6;
 #pragma unroll
     for (uint32_t k = 0; k < 4; k++) s_w[k][t] = 0u;
     __syncthreads();
     uint32_t bk[kPartRounds];
-    wave_hist(SortDigit<kFirst>{src, shift}, count, 8u, (uint64_t)blockIdx.x * kPartTile + (uint64_t)wv * (kPartTile / 4u),
+    wave_hist(SortDigit<kFirst, kOrdered>{src, order, count, shift}, count, 8u, (uint64_t)blockIdx.x * kPartTile + (uint64_t)wv * (kPartTile / 4u),
               s_w[wv], bk);
     __syncthreads();
     hist[(uint64_t)t * T + blockIdx.x] = s_w[0][t] + s_w[1][t] + s_w[2][t] + s_w[3][t];
@@ -407,16 +418,16 @@ __global__ __launch_bounds__(256) void k_sort_count(const void* src, uint64_t co
 // time for the store (its tile's 8 KiB were read a moment ago); whatever the
 // source holds by then, the position comes from the parked order and is
 // checked against `count`.
-template <bool kFirst, bool kLast>
-__global__ __launch_bounds__(256) void k_sort_scatter(const void* src, uint64_t count, uint32_t shift, uint64_t T,
-                                                      const uint32_t* base, uint64_t* dst, uint32_t* out_index) {
+template <bool kFirst, bool kLast, bool kOrdered = false>
+__global__ __launch_bounds__(256) void k_sort_scatter(const void* src, const uint32_t* order, uint64_t count, uint32_t shift,
+                                                      uint64_t T, const uint32_t* base, uint64_t* dst, uint32_t* out_index) {
     __shared__ uint32_t s_w[4][256];
     __shared__ uint32_t s_ord[kPartTile];
     __shared__ uint32_t s_delta[256];
     __shared__ uint32_t s_ws[4];
     const uint32_t t = threadIdx.x;
     const uint64_t tile0 = (uint64_t)blockIdx.x * kPartTile;
-    const SortDigit<kFirst> digit{src, shift};
+    const SortDigit<kFirst, kOrdered> digit{src, order, count, shift};
     tile_bucket_order(digit, count, 256u, 8u, T, base, s_w, s_ord, s_delta, s_ws);
 #pragma unroll
     for (uint32_t r = 0; r < kPartRounds; r++) {
@@ -434,7 +445,11 @@ __global__ __launch_bounds__(256) void k_sort_scatter(const void* src, uint64_t 
     }
 }
 
-hipError_t launch_flow_sort(const nexg_flow* flows, uint64_t count, uint32_t* out_index, void* workspace, hipStream_t s) {
+// rows: `count` u64, the 32-bit key in the low word. start: nullptr, or the
+// order the chain starts from (it may be out_index: the first pass reads it,
+// the last writes).
+hipError_t launch_radix_sort(const void* rows, const uint32_t* start, uint64_t count, uint32_t* out_index, void* workspace,
+                             hipStream_t s) {
     if (count == 0) return hipSuccess;
     const FlowSortLayout w = FlowSortLayout::from(count);
     const uint64_t T = w.tiles;
@@ -443,22 +458,30 @@ hipError_t launch_flow_sort(const nexg_flow* flows, uint64_t count, uint32_t* ou
     uint64_t* pong = region<uint64_t>(workspace, w.pong);
     const dim3 gT((uint32_t)T), b(kTile);
     for (uint32_t pass = 0; pass < 4; pass++) {
-        const void* src = pass == 0 ? static_cast<const void*>(flows) : (pass & 1u) ? ping : pong;
+        const void* src = pass == 0 ? rows : (pass & 1u) ? ping : pong;
         uint64_t* dst = (pass & 1u) ? pong : ping;
         const uint32_t shift = 8u * pass;
-        if (pass == 0)
-            hipLaunchKernelGGL(k_sort_count<true>, gT, b, 0, s, src, count, shift, T, hist);
+        if (pass == 0 && start)
+            hipLaunchKernelGGL((k_sort_count<true, true>), gT, b, 0, s, src, start, count, shift, T, hist);
+        else if (pass == 0)
+            hipLaunchKernelGGL(k_sort_count<true>, gT, b, 0, s, src, start, count, shift, T, hist);
         else
-            hipLaunchKernelGGL(k_sort_count<false>, gT, b, 0, s, src, count, shift, T, hist);
+            hipLaunchKernelGGL(k_sort_count<false>, gT, b, 0, s, src, start, count, shift, T, hist);
         launch_counter_scan(hist, w.counters, region<uint32_t>(workspace, w.sums), region<uint64_t>(workspace, w.total), s);
-        if (pass == 0)
-            hipLaunchKernelGGL((k_sort_scatter<true, false>), gT, b, 0, s, src, count, shift, T, hist, dst, out_index);
+        if (pass == 0 && start)
+            hipLaunchKernelGGL((k_sort_scatter<true, false, true>), gT, b, 0, s, src, start, count, shift, T, hist, dst, out_index);
+        else if (pass == 0)
+            hipLaunchKernelGGL((k_sort_scatter<true, false>), gT, b, 0, s, src, start, count, shift, T, hist, dst, out_index);
         else if (pass < 3)
-            hipLaunchKernelGGL((k_sort_scatter<false, false>), gT, b, 0, s, src, count, shift, T, hist, dst, out_index);
+            hipLaunchKernelGGL((k_sort_scatter<false, false>), gT, b, 0, s, src, start, count, shift, T, hist, dst, out_index);
         else
-            hipLaunchKernelGGL((k_sort_scatter<false, true>), gT, b, 0, s, src, count, shift, T, hist, dst, out_index);
+            hipLaunchKernelGGL((k_sort_scatter<false, true>), gT, b, 0, s, src, start, count, shift, T, hist, dst, out_index);
     }
     return hipGetLastError();
+}
+
+hipError_t launch_flow_sort(const nexg_flow* flows, uint64_t count, uint32_t* out_index, void* workspace, hipStream_t s) {
+    return launch_radix_sort(flows, nullptr, count, out_index, workspace, s);
 }
 
 // ---- groups ------------------------------------------------------------------------------

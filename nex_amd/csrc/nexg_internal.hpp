@@ -197,6 +197,23 @@ hipError_t launch_flow_partition(const ParseArgs& a, const nexg_flow* flows, uin
 // nexg_flow_sort / nexg_flow_groups (nexg_flow.hip); the workspaces as
 // nexg_flow_sort_workspace / nexg_flow_groups_workspace lay them out
 hipError_t launch_flow_sort(const nexg_flow* flows, uint64_t count, uint32_t* out_index, void* workspace, hipStream_t s);
+// The sort's four passes over any rows (`count` u64, the 32-bit key in the low
+// word), from the table's order (start nullptr) or from the order a chain
+// before left in `start` (which may be out_index): a sort by two keys is two
+// chains, the minor key first. The workspace is nexg_flow_sort_workspace's.
+hipError_t launch_radix_sort(const void* rows, const uint32_t* start, uint64_t count, uint32_t* out_index, void* workspace,
+                             hipStream_t s);
+
+// nexg_reasm_plan / nexg_reasm_frames / nexg_reasm_held (nexg_reasm.hip).
+// workspace: as nexg_reasm_plan_workspace (workspace_layout.hpp
+// ReasmPlanLayout) and nexg_select_workspace (TileCountLayout) size it.
+hipError_t launch_reasm_plan(const ParseArgs& a, uint32_t align, uint32_t* out_first, uint64_t* out_bytes, nexg_reasm* rows,
+                             void* workspace, hipStream_t s);
+hipError_t launch_reasm_frames(const ParseArgs& a, uint32_t align, const nexg_reasm* rows, const uint32_t* out_first,
+                               const uint64_t* out_bytes, uint64_t out_count, uint64_t* out_offsets, uint32_t* out_len,
+                               uint32_t* out_src, uint8_t* out_data, uint64_t out_cap, hipStream_t s);
+hipError_t launch_reasm_held(const ParseArgs& a, const nexg_reasm* rows, uint32_t* out_index, uint64_t* out_off,
+                             uint32_t* out_len, uint64_t* out_count, void* workspace, hipStream_t s);
 hipError_t launch_flow_groups(const ParseArgs& a, const nexg_record* recs, const nexg_flow* flows, uint32_t opt,
                               const uint32_t* order, nexg_flow_group* out, uint64_t groups_cap, uint32_t* out_group,
                               uint64_t* out_count, void* workspace, hipStream_t s);

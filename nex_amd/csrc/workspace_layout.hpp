@@ -135,6 +135,47 @@ struct FlowGroupsLayout {
     }
 };
 
+// nexg_reasm_plan_workspace: the sort's workspace (rounded up to 16 B), the
+// 32-B classifications, the 8-B regions, then the u32 tables (an even number
+// of slots each)
+struct ReasmPlanLayout {
+    uint64_t tiles;        // of 256 frames, and of 256 sorted positions
+    uint64_t sort;         // FlowSortLayout::from(count)
+    uint64_t info;         // 32 B per frame, 16-B aligned
+    uint64_t key_idfo;     // u64[count]: id << 13 | fo in the low word
+    uint64_t key_hash;     // u64[count]: the hash in the low word
+    uint64_t mark;         // u64[count]
+    uint64_t tile_bb;      // u64[tiles]: breaks | bad << 32
+    uint64_t tile_frames;  // u64[tiles]
+    uint64_t tile_bytes;   // u64[tiles]
+    uint64_t totals;       // u64[4]: groups, breaks | bad << 32, output frames, spare
+    uint64_t order;        // u32[count]
+    uint64_t out_len;      // u32[count]
+    uint64_t starts;       // u32[count]
+    uint64_t tile_heads;   // u32[tiles]
+    uint64_t bytes;
+    static ReasmPlanLayout from(uint64_t count) {
+        ReasmPlanLayout w;
+        w.tiles = (count + 255u) / 256u;
+        const uint64_t even = (count + 1u) & ~(uint64_t)1u, even_tiles = (w.tiles + 1u) & ~(uint64_t)1u;
+        w.sort = 0;
+        w.info = (FlowSortLayout::from(count).bytes + 15u) & ~(uint64_t)15u;
+        w.key_idfo = w.info + 32u * count;
+        w.key_hash = w.key_idfo + 8u * count;
+        w.mark = w.key_hash + 8u * count;
+        w.tile_bb = w.mark + 8u * count;
+        w.tile_frames = w.tile_bb + 8u * w.tiles;
+        w.tile_bytes = w.tile_frames + 8u * w.tiles;
+        w.totals = w.tile_bytes + 8u * w.tiles;
+        w.order = w.totals + 32u;
+        w.out_len = w.order + 4u * even;
+        w.starts = w.out_len + 4u * even;
+        w.tile_heads = w.starts + 4u * even;
+        w.bytes = w.tile_heads + 4u * even_tiles;
+        return w;
+    }
+};
+
 // nexg_flow_table_workspace: a u64 per position of the merged order, then a
 // u32 per 256-position tile (an even number of slots)
 struct FlowTableLayout {
